@@ -7,7 +7,7 @@ MIGT pass with the MASK view -> argmax -> decode -> uint8 novel view (+ the loca
 Workload = BASELINE.json configs[1]: SM7 codebook + transformer, 6 context views -> 1 novel view, bf16: the encoder and the codebook
 lookup stay exact fp32 (bit-exact token indices), the transformer's dense layers and the decoder's convolutions run on bf16 MFMA with
 fp32 accumulation (--precision f32 runs the all-fp32 parity arm).  Inputs are resident in HBM when the timed region starts and the
-generated images stay in HBM (``host_io`` in the line reports the rate with the host round trip the reference's loop makes).
+generated images stay in HBM (with --full, ``host_io`` in the line reports the rate with the host round trip the reference's loop makes).
 
   python bench.py --gpus N --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -21,6 +21,12 @@ Other workloads through the same contract (one JSON line, barrier + max-over-ran
 
 N>1: one process per GPU, scenes sharded (weak scaling: --batch scenes per GPU per step), weights replicated, no data-path
 collective on the inference workloads; rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+Everything measured beside the headline — the host round trip, the per-kernel roofline sections, the all-fp32 arm, the CPU baseline,
+the training line's collective cost — takes runs of its own and is reported only with --full.
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the timed path handed its caller in its last step as DIR/<name>.npy
+                      (float32, float64 where the array is float64; at most 64 MB, larger outputs as a fixed seeded sample of rows)
 """
 import argparse
 import json
@@ -271,6 +277,39 @@ def _tail_on():
     return bool(_lib.load().vf_selected(_lib.SEL_GEMM_TAIL))
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: ``arrays`` (name -> tensor or number) as ``out_dir/<name>.npy``, float64 arrays as float64 and everything else as
+    float32.  When the arrays together exceed DUMP_BUDGET_BYTES, each one is cut to the same fraction of its leading-axis rows, chosen by a
+    generator seeded with ``seed``: the same rows in every run with the same arguments."""
+    import numpy as np
+    arrs = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu()
+            a = v.double().numpy() if v.dtype == torch.float64 else v.float().numpy()
+        elif isinstance(v, (int, float, list, tuple, np.ndarray, np.number)):
+            a = np.asarray(v)
+            a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        else:
+            continue
+        arrs[name] = np.atleast_1d(a)
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in sorted(arrs.items()):
+        if total > DUMP_BUDGET_BYTES:
+            n = a.shape[0]
+            keep = max(1, n * DUMP_BUDGET_BYTES // total)
+            if keep < n:
+                a = a[np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+        written += a.nbytes
+    sys.stderr.write(f'bench.py: {len(arrs)} output arrays ({written / 1e6:.1f} MB) written to {out_dir}\n')
+
+
 def timed(step, steps, warmup, dev):
     """the contract's timed region: W warm-up steps, then exactly K steps between barrier + synchronize, max over ranks"""
     from viewformer_amd import sharding
@@ -313,9 +352,11 @@ def run_train(args, rank, local, world, dev):
         tr.overlap_weight_gradients = False
     tr.train_step(poses, tokens)                                       # setup (allocator, code objects), untimed
     dt, met = timed(lambda: tr.train_step(poses, tokens), args.steps, args.warmup, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, met)
     scenes = sharding.sum_over_ranks(B * args.steps, dev)
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         # what the collective costs: the same step without it, and the compute stream's wait for the per-layer all-reduces after the
         # last backward kernel (the part the overlap with the backward pass did not hide), averaged over the timed step count
         dt_off, _ = timed(lambda: tr.train_step(poses, tokens, reduce_gradients=False), args.steps, 1, dev)
@@ -332,33 +373,7 @@ def run_train(args, rank, local, world, dev):
                         'last backward kernel (HIP events), max over ranks'}
     if rank != 0:
         return
-    # GEMM-family roofline: every launch timed by HIP events on the stream it is issued to, with the weight-gradient GEMMs back on the
-    # MAIN stream for this one instrumented step (tr.overlap_weight_gradients off).  In the timed steps gemm_tn_bf16 runs on a second
-    # stream beside the dX GEMM: two concurrent kernels share the CUs, each one's begin-to-end time stretches, and a sum of such
-    # durations counts the overlap twice (round 4's line: 20.5 "kernel ms" inside a 21.2 ms step).  Serialised, a launch's duration is its
-    # own, the sum is the family's time, and it is comparable with a rocprofv3 kernel trace of `--serial-wgrad` (profiles/r5_*)
-    overlap = tr.overlap_weight_gradients
-    tr.overlap_weight_gradients = False
-    tr.train_step(poses, tokens, reduce_gradients=False)              # rank 0 alone from here on: no collective (the other ranks have returned)
-    best = None
-    for _ in range(2):                                                # two instrumented steps, the smaller total kept (clock drift after the timed loop)
-        prof = OpTimer()
-        prof.install()
-        tr.train_step(poses, tokens, reduce_gradients=False)
-        res = prof.gemm_summary()
-        prof.uninstall()
-        if best is None or res[0] < best[0]:
-            best = res
-    ms, fl, n, top = best
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(3):
-        tr.train_step(poses, tokens, reduce_gradients=False)
-    torch.cuda.synchronize()
-    serial_step_ms = (time.perf_counter() - t0) / 3 * 1e3
-    tr.overlap_weight_gradients = overlap
     grad_mb = sum(int(t.numel()) for t in [tr.flat_g]) * 4 / 2 ** 20
-    peak = BF16_MFMA_PEAK_TFLOPS if arm == 'bf16' else BF16_MFMA_PEAK_TFLOPS / 6
     line = {'metric': 'MIGT training scenes/sec (3-stream forward, losses, backward, AdamWeightDecay), CO3D 10-cat finetune config',
             'value': round(scenes / dt, 3), 'unit': 'scenes/s', 'n_gpus': world, 'shared_device': args.dist['shared_device'], 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
@@ -373,28 +388,55 @@ def run_train(args, rank, local, world, dev):
                                        'epilogues / LayerNorm backward / flash attention kernels of the bf16 arm',
                        'precision': ('fp32 master weights, bf16-MFMA dense GEMMs (the reference trains with --fp16)' if arm == 'bf16' else
                                      'fp32-equivalent: x3h forward GEMMs, x6 backward GEMMs, x6 / f32 attention'),
-                       'weights': 'random-init MIGT 88.4M', 'loss': float(met['loss']), 'collective': comm},
-            'roofline': {'bound': 'mfma', 'kernel': 'dense GEMM family of the step (gemm_bf16 / gemm_bf16_g256 / gemm_tn_bf16 or gemm_x3h / gemm_x6 launches: forward, dX, dW incl. its slab sums)',
-                         'achieved': round(fl / (ms * 1e-3) / 1e12, 2), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
-                         'frac': round(fl / (ms * 1e-3) / 1e12 / peak, 4),
-                         # HBM bytes of the family's largest launch shape (c_fc forward and its dX twin, 900 tiles: the same algorithmic bytes) from
-                         # this round's committed counter passes
-                         'traffic': (lambda t, alg: None if t is None else {
-                             'launch': '19 200 x 768 x 3072 with bf16 in / out (c_fc forward with its GELU-dual epilogue; mlp.c_proj dX with its GELU-backward epilogue)',
-                             'bytes': t['bytes'], 'algorithmic_bytes': alg, 'over_algorithmic': round(t['bytes'] / alg, 3), 'source': t['source']})(
-                             pmc_traffic('gemm_bf16_g256_kernelILb1ELb0E', (64 + 15) * 12 if _tail_on() else 900, 512, 'train')
-                             if (arm == 'bf16' and (B, S) == (10, 10)) else None, 19200 * 768 * 2 + 768 * 3072 * 2 + 2 * 19200 * 3072 * 2),
-                         'launches_per_step': n,
-                         'kernel_ms_per_step': round(ms, 3), 'algorithmic_gflop_per_step': round(fl / 1e9, 1),
-                         'timing': 'HIP events on the launch stream around every GEMM-family launch of ONE step run with the weight-gradient '
-                                   'GEMMs serialised on the main stream (no concurrent kernel stretches a duration); the timed steps overlap '
-                                   'them on a second stream',
-                         'ms_per_step_serialised': round(serial_step_ms, 3),
-                         'weight_gradient_stream_overlap_in_timed_steps': bool(overlap),
-                         'top_shapes_mode_M_K_N_batch': [{'shape': list(k), 'ms': round(v[0], 3), 'tflops': round(v[1] / (v[0] * 1e-3) / 1e12, 1),
-                                                          'launches': v[2]} for k, v in top],
-                         'peak_note': 'fp32-equivalent GEMMs execute 3 (x3h) or 6 (x6) 16-bit MFMA flops per fp32 flop; peak quoted = 2500 / 6'
-                                      if arm != 'bf16' else 'dense bf16 MFMA peak'}}
+                       'weights': 'random-init MIGT 88.4M', 'loss': float(met['loss']), 'collective': comm}}
+    if args.full:
+        # GEMM-family roofline: every launch timed by HIP events on the stream it is issued to, with the weight-gradient GEMMs back on the
+        # MAIN stream for this one instrumented step (tr.overlap_weight_gradients off).  In the timed steps gemm_tn_bf16 runs on a second
+        # stream beside the dX GEMM: two concurrent kernels share the CUs, each one's begin-to-end time stretches, and a sum of such
+        # durations counts the overlap twice (round 4's line: 20.5 "kernel ms" inside a 21.2 ms step).  Serialised, a launch's duration is its
+        # own, the sum is the family's time, and it is comparable with a rocprofv3 kernel trace of `--serial-wgrad` (profiles/r5_*)
+        overlap = tr.overlap_weight_gradients
+        tr.overlap_weight_gradients = False
+        tr.train_step(poses, tokens, reduce_gradients=False)              # rank 0 alone from here on: no collective (the other ranks have returned)
+        best = None
+        for _ in range(2):                                                # two instrumented steps, the smaller total kept (clock drift after the timed loop)
+            prof = OpTimer()
+            prof.install()
+            tr.train_step(poses, tokens, reduce_gradients=False)
+            res = prof.gemm_summary()
+            prof.uninstall()
+            if best is None or res[0] < best[0]:
+                best = res
+        ms, fl, n, top = best
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            tr.train_step(poses, tokens, reduce_gradients=False)
+        torch.cuda.synchronize()
+        serial_step_ms = (time.perf_counter() - t0) / 3 * 1e3
+        tr.overlap_weight_gradients = overlap
+        peak = BF16_MFMA_PEAK_TFLOPS if arm == 'bf16' else BF16_MFMA_PEAK_TFLOPS / 6
+        line['roofline'] = {'bound': 'mfma', 'kernel': 'dense GEMM family of the step (gemm_bf16 / gemm_bf16_g256 / gemm_tn_bf16 or gemm_x3h / gemm_x6 launches: forward, dX, dW incl. its slab sums)',
+                            'achieved': round(fl / (ms * 1e-3) / 1e12, 2), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
+                            'frac': round(fl / (ms * 1e-3) / 1e12 / peak, 4),
+                            # HBM bytes of the family's largest launch shape (c_fc forward and its dX twin, 900 tiles: the same algorithmic bytes) from
+                            # this round's committed counter passes
+                            'traffic': (lambda t, alg: None if t is None else {
+                                'launch': '19 200 x 768 x 3072 with bf16 in / out (c_fc forward with its GELU-dual epilogue; mlp.c_proj dX with its GELU-backward epilogue)',
+                                'bytes': t['bytes'], 'algorithmic_bytes': alg, 'over_algorithmic': round(t['bytes'] / alg, 3), 'source': t['source']})(
+                                pmc_traffic('gemm_bf16_g256_kernelILb1ELb0E', (64 + 15) * 12 if _tail_on() else 900, 512, 'train')
+                                if (arm == 'bf16' and (B, S) == (10, 10)) else None, 19200 * 768 * 2 + 768 * 3072 * 2 + 2 * 19200 * 3072 * 2),
+                            'launches_per_step': n,
+                            'kernel_ms_per_step': round(ms, 3), 'algorithmic_gflop_per_step': round(fl / 1e9, 1),
+                            'timing': 'HIP events on the launch stream around every GEMM-family launch of ONE step run with the weight-gradient '
+                                      'GEMMs serialised on the main stream (no concurrent kernel stretches a duration); the timed steps overlap '
+                                      'them on a second stream',
+                            'ms_per_step_serialised': round(serial_step_ms, 3),
+                            'weight_gradient_stream_overlap_in_timed_steps': bool(overlap),
+                            'top_shapes_mode_M_K_N_batch': [{'shape': list(k), 'ms': round(v[0], 3), 'tflops': round(v[1] / (v[0] * 1e-3) / 1e12, 1),
+                                                             'launches': v[2]} for k, v in top],
+                            'peak_note': 'fp32-equivalent GEMMs execute 3 (x3h) or 6 (x6) 16-bit MFMA flops per fp32 flop; peak quoted = 2500 / 6'
+                                         if arm != 'bf16' else 'dense bf16 MFMA peak'}
     print(json.dumps(line), flush=True)
 
 
@@ -423,12 +465,15 @@ def run_allimg(args, rank, local, world, dev):
     n_img = sharding.sum_over_ranks(F * S * args.steps, dev)
     if rank != 0:
         return
-    prof = OpTimer()
-    prof.install()
-    step()
-    torch.cuda.synchronize()
-    att = prof.attn_entry()
-    prof.uninstall()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+    if args.full:
+        prof = OpTimer()
+        prof.install()
+        step()
+        torch.cuda.synchronize()
+        att = prof.attn_entry()
+        prof.uninstall()
     line = {'metric': 'generated views/sec, all-images evaluator loop (encode sequence -> multi-context transformer -> decode), 128px',
             'value': round(n_img / dt, 3), 'unit': 'generated views/s', 'n_gpus': world, 'shared_device': args.dist['shared_device'], 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
@@ -441,8 +486,9 @@ def run_allimg(args, rank, local, world, dev):
                        'frames_per_sequence': F, 'views_per_scene': S, 'transformer_batch': ea.TRANSFORMER_BATCH,
                        'decode_batch_scenes': ea.DECODE_BATCH, 'images_decoded_per_step': F * S, 'attention': tr.attention,
                        'parallelism': f'sequence-shard x{world}, no collective', 'ranks': args.dist['ranks'],
-                       'backend': args.dist['backend'], 'dist': args.dist},
-            'roofline': att or {}}
+                       'backend': args.dist['backend'], 'dist': args.dist}}
+    if args.full:
+        line['roofline'] = att or {}
     print(json.dumps(line), flush=True)
 
 
@@ -597,8 +643,16 @@ def main():
     ap.add_argument('--batch-sweep', default=None,
                     help='views workload: comma-separated scenes-per-step list (SURVEY 8d: 1,8,64,256,1024); prints ONE JSON line with the '
                          'views/s of every batch size (same models, inputs resident in HBM, --steps timed steps each)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need, each in runs of its own: the host round trip, the roofline sections '
+                         '(per-kernel HIP-event timing), the all-fp32 arm, the CPU baseline, and the training line\'s collective cost')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB: '
+                         'larger outputs as a fixed seeded sample of rows); rank 0\'s shard')
     args = ap.parse_args()
     args.batch_set, args.views_set = args.batch is not None, args.views is not None
+    if args.dump_outputs and args.batch_sweep:
+        ap.error('--dump-outputs: the batch sweep times several paths; run one --batch instead')
 
     from viewformer_amd import sharding
     from viewformer_amd.evaluate import generate_batch_predictions
@@ -687,6 +741,8 @@ def main():
     dt, out = timed(step, args.steps, args.warmup, dev)
     views = sharding.sum_over_ranks(B * args.steps, dev)
     assert out['generated_images'].dtype == torch.uint8
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     if rank != 0:
         sharding.barrier()
@@ -708,7 +764,7 @@ def main():
                    'target_view_encoded': True, 'parallelism': f'scene-shard x{world}, no collective',
                    'ranks': args.dist['ranks'], 'backend': args.dist['backend'], 'dist': args.dist,
                    'io': 'inputs (uint8 frames, cameras) resident in HBM when the timed region starts; generated uint8 images stay in HBM '
-                         '(see host_io for the rate with the host round trip)',
+                         '(with --full, host_io reports the rate with the host round trip)',
                    'precision': ('fp32 everywhere' if args.precision == 'f32' else
                                  'mixed: fp32 encoder + codebook lookup (bit-exact tokens), bf16-MFMA transformer dense '
                                  f'layers + decoder convs (fp32 accumulate; tolerances in tests/test_hip_bf16.py), {tr.attention} attention'),
@@ -726,127 +782,128 @@ def main():
                    'reference_equivalent_note': 'views/s x the FLOPs of the REFERENCE loop per view (two transformer passes); the fused twin-view '
                                                 'pass executes 8/14 of the transformer part, so this is equivalent work, not executed FLOPs'},
     }
-    # ---- host round trip (the reference moves frames to the device and images back every batch, evaluate_transformer.py:18-19,222)
-    from viewformer_amd.evaluate import stream_batch_predictions
-    fr_h = torch.from_numpy(frames).pin_memory()
-    cm_h = torch.from_numpy(cams).pin_memory()
-    n_io = max(args.steps, 4)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for o in stream_batch_predictions(tr, vq, ((fr_h, cm_h) for _ in range(n_io))):
-        img_h = o['generated_images']                  # host tensors (pinned ring)
-    host_dt = (time.perf_counter() - t0) / n_io
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n_io):                              # the resident loop again, right beside it (clocks drift between the phases of a run)
-        step()
-    torch.cuda.synchronize()
-    resident_dt = (time.perf_counter() - t0) / n_io
-    t0 = time.perf_counter()
-    for _ in range(2):
-        o = generate_batch_predictions(tr, vq, fr_h.to(dev, non_blocking=True), cm_h.to(dev, non_blocking=True))
-        img_s, cam_s = o['generated_images'].cpu(), o['generated_cameras'].cpu()
-    serial_dt = (time.perf_counter() - t0) / 2
-    line['host_io'] = {'value': round(B / host_dt, 2), 'unit': 'novel views/s', 'steps': n_io,
-                       'serial_value': round(B / serial_dt, 2), 'resident_value_same_phase': round(B / resident_dt, 2),
-                       'note': f'the evaluator\'s outer loop with host tensors in and out (evaluate.stream_batch_predictions): {fr_h.numel() >> 20} MiB of frames up '
-                               f'and {img_h.numel() >> 20} MiB of generated images down per step on a second HIP stream, overlapped with the neighbouring '
-                               'steps\' kernels; serial_value = the same copies issued in line with the step (the reference\'s loop); never the headline value'}
-    del img_s, cam_s
-    # ---- roofline section (rank 0): HIP events on the launch stream around every GEMM-family launch, the lookup and the attention
-    # two instrumented passes, the one with the smaller total kept: the first launches after the timed loop occasionally run
-    # at a lower clock (seen once: 5.5 ms instead of 3.7 ms for the dominant launch while the rocprofv3 trace said 3.75 ms)
-    best, prof_best = None, None
-    for _ in range(2):
-        prof = OpTimer()
-        prof.install()
-        step()
-        res = prof.gemm_summary()
-        prof.uninstall()
-        if best is None or res[0] < best[0]:
-            best, prof_best = res, prof
-    ms, fl, n, top = best
-    fam = fl / (ms * 1e-3) / 1e12
-    # dominant kernel = the halo-tile 3x3 conv at its dominant launch shape: 128->128 @128x128 (mode 1,
-    # M = images*128*128): SURVEY §8(d) per-unit figure 2*9*128*128 FLOP per output pixel x M pixels.
-    dom_key, dom = max(((k, v) for k, v in top if k[0] == 1), key=lambda kv: kv[1][0], default=(None, None))
-    if dom is None:
-        dom_key, dom = top[0]
-    d_ms = dom[0] / dom[2]                               # average launch duration (HIP events, launch stream)
-    d_fl = dom[1] / dom[2]                               # algorithmic (fp32 conv) FLOP per launch
-    ach = d_fl / (d_ms * 1e-3) / 1e12
-    x6 = args.conv_arith in ('x6', 'x3h')
-    nprod = {'x3h': 3, 'x6': 6, 'f32': 1}[args.conv_arith]
-    from viewformer_amd import _lib as _vflib
-    k32 = bool(_vflib.load().vf_selected(_vflib.SEL_CONV_X3H_K32))
-    is_dom_shape = dom_key[0] == 1 and tuple(dom_key[2:4]) == (128, 128)
-    # algorithmic bytes of a launch: x read once + out written once (+ the residual read once: ResnetBlock's conv2 — half of this shape's launches)
-    alg_nores, alg_res = dom_key[1] * (dom_key[2] + dom_key[3]) * 4, dom_key[1] * (dom_key[2] + 2 * dom_key[3]) * 4
-    alg_bytes, pmc, pmc_detail = alg_res, None, None
-    if is_dom_shape and args.conv_arith == 'x3h' and k32:
-        wgs = dom_key[1] // 128 * (dom_key[3] // 128)
-        # (one kernel instantiation serves conv1 — no residual — and conv2 of a ResnetBlock: the PMC mean is over both kinds, and so is the
-        # algorithmic figure it is compared with: half of this shape's launches read a residual)
-        pmc = pmc_traffic('conv3_halo_x3h16_kernelILb1ELb1E', wgs)
-        alg_bytes = (alg_res + alg_nores) // 2
-        if pmc:
-            pmc_detail = {'read': pmc['read_bytes'], 'written': pmc['written_bytes'], 'dispatches': pmc['dispatches'],
-                          'algorithmic_bytes_with_residual': alg_res, 'algorithmic_bytes_without_residual': alg_nores}
-    # x6 executes 6 bf16 MFMA flops per algorithmic fp32 flop, so its ceiling in algorithmic terms is bf16_peak / 6
-    peak = BF16_MFMA_PEAK_TFLOPS / nprod if x6 else F32_MFMA_PEAK_TFLOPS      # dense f16 peak == dense bf16 peak (2.5 PF)
-    line['roofline'] = {'bound': 'mfma',
-                        'kernel': (('conv3_halo_x3h16_kernel<GN+swish> (3x3 conv 128->128 @128x128, 3x v_mfma_f32_16x16x32_f16 per fp32 product)'
-                                    if k32 else 'conv3_halo_x3h_kernel<s1,GN+swish> (3x3 conv 128->128 @128x128, 3x v_mfma_f32_32x32x16_f16 per fp32 '
-                                    'product; vf_select(VF_SEL_CONV_X3H_K32, 0))') if nprod == 3 else
-                                   'conv3_halo_x6_kernel<s1,GN+swish> (3x3 conv 128->128 @128x128, 6x v_mfma_f32_32x32x16_bf16 '
-                                   'per fp32 product)' if x6 else
-                                   'conv3_halo_kernel<s1,GN+swish> (3x3 conv 128->128 @128x128, v_mfma_f32_32x32x2_f32)'),
-                        'achieved': round(ach, 2), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
-                        'frac': round(ach / peak, 4),
-                        'peak_note': (f'algorithmic fp32 TFLOP/s; peak = dense 16-bit MFMA peak 2500 / {nprod} partial products. Executed '
-                                      f'16-bit rate {round(nprod * ach, 1)} TFLOP/s; the native f32 MFMA peak is {F32_MFMA_PEAK_TFLOPS}.  On full-entropy '
-                                      f'operands the matrix pipe alone draws the package power limit at {F16_MFMA_POWER_LIMITED_TFLOPS} TFLOP/s (f16; '
-                                      f'bf16 {BF16_MFMA_POWER_LIMITED_TFLOPS}; profiles/r4_power_ceiling_probe.txt): the executed rate is '
-                                      f'{round(nprod * ach / (F16_MFMA_POWER_LIMITED_TFLOPS if nprod == 3 else BF16_MFMA_POWER_LIMITED_TFLOPS), 3)} of that'
-                                      if x6 else 'dense f32 MFMA peak'),
-                        'traffic': (pmc['bytes'] if pmc else None),
-                        'traffic_unit': 'bytes/launch',
-                        'traffic_over_algorithmic_bytes': (round(pmc['bytes'] / alg_bytes, 4) if pmc else None),
-                        'traffic_by_launch_kind': pmc_detail,
-                        'traffic_source': (pmc['source'] if pmc else 'no committed PMC pass for this launch shape'),
-                        'launch_shape_mode_M_Cin_Cout_batch': list(dom_key), 'avg_launch_ms': round(d_ms, 4),
-                        'algorithmic_gflop_per_launch': round(d_fl / 1e9, 1),
-                        'algorithmic_bytes_per_launch': alg_bytes,
-                        'family': {'kernels': 'every conv/dense launch of the step (conv3_halo_x3h/_x6/_bf16/_f32, igemm_f32, gemm_bf16, gemm_x6)',
-                                   'achieved': round(fam, 2),
-                                   'launches_per_step': n, 'kernel_ms_per_step': round(ms, 3),
-                                   'algorithmic_gflop_per_step': round(fl / 1e9, 1)},
-                        'top_shapes_mode_M_Cin_Cout_batch': [
-                            {'shape': list(k), 'ms': round(v[0], 3), 'tflops': round(v[1] / (v[0] * 1e-3) / 1e12, 1),
-                             'launches': v[2]} for k, v in top],
-                        # the two kernels the north star names beside the dominant one, measured in the same instrumented step
-                        'codebook_lookup': prof_best.vq_entry(), 'attention': prof_best.attn_entry()}
-    # ---- the all-fp32 parity arm, timed briefly beside the headline (mixed) arm
-    if args.precision == 'mixed' and not args.no_f32_arm and world == 1:
-        del out, o
-        vq32, tr32, _ = build_models(dev, localization, 'f32', args.conv_arith, True, args.encoder_chunk)
-
-        def step32():
-            return generate_batch_predictions(tr32, vq32, frames_d, cams_d)
-        step32()
+    if args.full:
+        # ---- host round trip (the reference moves frames to the device and images back every batch, evaluate_transformer.py:18-19,222)
+        from viewformer_amd.evaluate import stream_batch_predictions
+        fr_h = torch.from_numpy(frames).pin_memory()
+        cm_h = torch.from_numpy(cams).pin_memory()
+        n_io = max(args.steps, 4)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(2):
-            step32()
+        for o in stream_batch_predictions(tr, vq, ((fr_h, cm_h) for _ in range(n_io))):
+            img_h = o['generated_images']                  # host tensors (pinned ring)
+        host_dt = (time.perf_counter() - t0) / n_io
         torch.cuda.synchronize()
-        dt32 = (time.perf_counter() - t0) / 2
-        line['f32_arm'] = {'value': round(B / dt32, 2), 'unit': 'novel views/s', 'ms_per_step': round(dt32 * 1e3, 2), 'steps': 2,
-                           'note': 'everything fp32-equivalent (x3h / x6 convolutions and dense layers, x6 attention): the full-parity arm, '
-                                   'same workload, this GPU only'}
-        del vq32, tr32
-    if world == 1 and not args.no_cpu_baseline:
-        n_cpu = args.cpu_scenes or 8
-        line['cpu_baseline'] = cpu_baseline(models_cfg, S, n_cpu)
+        t0 = time.perf_counter()
+        for _ in range(n_io):                              # the resident loop again, right beside it (clocks drift between the phases of a run)
+            step()
+        torch.cuda.synchronize()
+        resident_dt = (time.perf_counter() - t0) / n_io
+        t0 = time.perf_counter()
+        for _ in range(2):
+            o = generate_batch_predictions(tr, vq, fr_h.to(dev, non_blocking=True), cm_h.to(dev, non_blocking=True))
+            img_s, cam_s = o['generated_images'].cpu(), o['generated_cameras'].cpu()
+        serial_dt = (time.perf_counter() - t0) / 2
+        line['host_io'] = {'value': round(B / host_dt, 2), 'unit': 'novel views/s', 'steps': n_io,
+                           'serial_value': round(B / serial_dt, 2), 'resident_value_same_phase': round(B / resident_dt, 2),
+                           'note': f'the evaluator\'s outer loop with host tensors in and out (evaluate.stream_batch_predictions): {fr_h.numel() >> 20} MiB of frames up '
+                                   f'and {img_h.numel() >> 20} MiB of generated images down per step on a second HIP stream, overlapped with the neighbouring '
+                                   'steps\' kernels; serial_value = the same copies issued in line with the step (the reference\'s loop); never the headline value'}
+        del img_s, cam_s
+        # ---- roofline section (rank 0): HIP events on the launch stream around every GEMM-family launch, the lookup and the attention
+        # two instrumented passes, the one with the smaller total kept: the first launches after the timed loop occasionally run
+        # at a lower clock (seen once: 5.5 ms instead of 3.7 ms for the dominant launch while the rocprofv3 trace said 3.75 ms)
+        best, prof_best = None, None
+        for _ in range(2):
+            prof = OpTimer()
+            prof.install()
+            step()
+            res = prof.gemm_summary()
+            prof.uninstall()
+            if best is None or res[0] < best[0]:
+                best, prof_best = res, prof
+        ms, fl, n, top = best
+        fam = fl / (ms * 1e-3) / 1e12
+        # dominant kernel = the halo-tile 3x3 conv at its dominant launch shape: 128->128 @128x128 (mode 1,
+        # M = images*128*128): SURVEY §8(d) per-unit figure 2*9*128*128 FLOP per output pixel x M pixels.
+        dom_key, dom = max(((k, v) for k, v in top if k[0] == 1), key=lambda kv: kv[1][0], default=(None, None))
+        if dom is None:
+            dom_key, dom = top[0]
+        d_ms = dom[0] / dom[2]                               # average launch duration (HIP events, launch stream)
+        d_fl = dom[1] / dom[2]                               # algorithmic (fp32 conv) FLOP per launch
+        ach = d_fl / (d_ms * 1e-3) / 1e12
+        x6 = args.conv_arith in ('x6', 'x3h')
+        nprod = {'x3h': 3, 'x6': 6, 'f32': 1}[args.conv_arith]
+        from viewformer_amd import _lib as _vflib
+        k32 = bool(_vflib.load().vf_selected(_vflib.SEL_CONV_X3H_K32))
+        is_dom_shape = dom_key[0] == 1 and tuple(dom_key[2:4]) == (128, 128)
+        # algorithmic bytes of a launch: x read once + out written once (+ the residual read once: ResnetBlock's conv2 — half of this shape's launches)
+        alg_nores, alg_res = dom_key[1] * (dom_key[2] + dom_key[3]) * 4, dom_key[1] * (dom_key[2] + 2 * dom_key[3]) * 4
+        alg_bytes, pmc, pmc_detail = alg_res, None, None
+        if is_dom_shape and args.conv_arith == 'x3h' and k32:
+            wgs = dom_key[1] // 128 * (dom_key[3] // 128)
+            # (one kernel instantiation serves conv1 — no residual — and conv2 of a ResnetBlock: the PMC mean is over both kinds, and so is the
+            # algorithmic figure it is compared with: half of this shape's launches read a residual)
+            pmc = pmc_traffic('conv3_halo_x3h16_kernelILb1ELb1E', wgs)
+            alg_bytes = (alg_res + alg_nores) // 2
+            if pmc:
+                pmc_detail = {'read': pmc['read_bytes'], 'written': pmc['written_bytes'], 'dispatches': pmc['dispatches'],
+                              'algorithmic_bytes_with_residual': alg_res, 'algorithmic_bytes_without_residual': alg_nores}
+        # x6 executes 6 bf16 MFMA flops per algorithmic fp32 flop, so its ceiling in algorithmic terms is bf16_peak / 6
+        peak = BF16_MFMA_PEAK_TFLOPS / nprod if x6 else F32_MFMA_PEAK_TFLOPS      # dense f16 peak == dense bf16 peak (2.5 PF)
+        line['roofline'] = {'bound': 'mfma',
+                            'kernel': (('conv3_halo_x3h16_kernel<GN+swish> (3x3 conv 128->128 @128x128, 3x v_mfma_f32_16x16x32_f16 per fp32 product)'
+                                        if k32 else 'conv3_halo_x3h_kernel<s1,GN+swish> (3x3 conv 128->128 @128x128, 3x v_mfma_f32_32x32x16_f16 per fp32 '
+                                        'product; vf_select(VF_SEL_CONV_X3H_K32, 0))') if nprod == 3 else
+                                       'conv3_halo_x6_kernel<s1,GN+swish> (3x3 conv 128->128 @128x128, 6x v_mfma_f32_32x32x16_bf16 '
+                                       'per fp32 product)' if x6 else
+                                       'conv3_halo_kernel<s1,GN+swish> (3x3 conv 128->128 @128x128, v_mfma_f32_32x32x2_f32)'),
+                            'achieved': round(ach, 2), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
+                            'frac': round(ach / peak, 4),
+                            'peak_note': (f'algorithmic fp32 TFLOP/s; peak = dense 16-bit MFMA peak 2500 / {nprod} partial products. Executed '
+                                          f'16-bit rate {round(nprod * ach, 1)} TFLOP/s; the native f32 MFMA peak is {F32_MFMA_PEAK_TFLOPS}.  On full-entropy '
+                                          f'operands the matrix pipe alone draws the package power limit at {F16_MFMA_POWER_LIMITED_TFLOPS} TFLOP/s (f16; '
+                                          f'bf16 {BF16_MFMA_POWER_LIMITED_TFLOPS}; profiles/r4_power_ceiling_probe.txt): the executed rate is '
+                                          f'{round(nprod * ach / (F16_MFMA_POWER_LIMITED_TFLOPS if nprod == 3 else BF16_MFMA_POWER_LIMITED_TFLOPS), 3)} of that'
+                                          if x6 else 'dense f32 MFMA peak'),
+                            'traffic': (pmc['bytes'] if pmc else None),
+                            'traffic_unit': 'bytes/launch',
+                            'traffic_over_algorithmic_bytes': (round(pmc['bytes'] / alg_bytes, 4) if pmc else None),
+                            'traffic_by_launch_kind': pmc_detail,
+                            'traffic_source': (pmc['source'] if pmc else 'no committed PMC pass for this launch shape'),
+                            'launch_shape_mode_M_Cin_Cout_batch': list(dom_key), 'avg_launch_ms': round(d_ms, 4),
+                            'algorithmic_gflop_per_launch': round(d_fl / 1e9, 1),
+                            'algorithmic_bytes_per_launch': alg_bytes,
+                            'family': {'kernels': 'every conv/dense launch of the step (conv3_halo_x3h/_x6/_bf16/_f32, igemm_f32, gemm_bf16, gemm_x6)',
+                                       'achieved': round(fam, 2),
+                                       'launches_per_step': n, 'kernel_ms_per_step': round(ms, 3),
+                                       'algorithmic_gflop_per_step': round(fl / 1e9, 1)},
+                            'top_shapes_mode_M_Cin_Cout_batch': [
+                                {'shape': list(k), 'ms': round(v[0], 3), 'tflops': round(v[1] / (v[0] * 1e-3) / 1e12, 1),
+                                 'launches': v[2]} for k, v in top],
+                            # the two kernels the north star names beside the dominant one, measured in the same instrumented step
+                            'codebook_lookup': prof_best.vq_entry(), 'attention': prof_best.attn_entry()}
+        # ---- the all-fp32 parity arm, timed briefly beside the headline (mixed) arm
+        if args.precision == 'mixed' and not args.no_f32_arm and world == 1:
+            del out, o
+            vq32, tr32, _ = build_models(dev, localization, 'f32', args.conv_arith, True, args.encoder_chunk)
+
+            def step32():
+                return generate_batch_predictions(tr32, vq32, frames_d, cams_d)
+            step32()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(2):
+                step32()
+            torch.cuda.synchronize()
+            dt32 = (time.perf_counter() - t0) / 2
+            line['f32_arm'] = {'value': round(B / dt32, 2), 'unit': 'novel views/s', 'ms_per_step': round(dt32 * 1e3, 2), 'steps': 2,
+                               'note': 'everything fp32-equivalent (x3h / x6 convolutions and dense layers, x6 attention): the full-parity arm, '
+                                       'same workload, this GPU only'}
+            del vq32, tr32
+        if world == 1 and not args.no_cpu_baseline:
+            n_cpu = args.cpu_scenes or 8
+            line['cpu_baseline'] = cpu_baseline(models_cfg, S, n_cpu)
     print(json.dumps(line), flush=True)
     sharding.barrier()
     if world > 1:

@@ -54,12 +54,12 @@ def test_views_workload_two_gpus_scene_shards():
 @two_gpus
 @pytest.mark.timeout(1500, method='thread')          # (launches of up to 420 s each: above conftest's 600 s default for GPU tests)
 def test_train_workload_two_gpus_rccl_allreduce():
-    line = _launch(['--workload', 'train', '--steps', '3', '--warmup', '1'], n=2)
+    line = _launch(['--workload', 'train', '--steps', '3', '--warmup', '1', '--full'], n=2)
     assert line['n_gpus'] == 2 and line['value'] > 0
     c = line['config']['collective']
     assert c['backend'] == 'nccl'                                               # RCCL
     assert c['ms_per_step_without_allreduce'] > 0 and c['exposed_allreduce_wait_ms'] >= 0
-    half = _launch(['--workload', 'train', '--steps', '3', '--warmup', '1', '--grad-dtype', 'bf16'], n=2)
+    half = _launch(['--workload', 'train', '--steps', '3', '--warmup', '1', '--grad-dtype', 'bf16', '--full'], n=2)
     assert half['config']['collective']['gradient_dtype_on_the_links'] == 'bf16' and half['value'] > 0
 
 
@@ -72,12 +72,12 @@ def test_two_rank_launch_line_on_one_gpu_over_gloo():
     views = _launch(['--steps', '2', '--warmup', '1', '--batch', '8', '--no-cpu-baseline', '--no-f32-arm'], n=2, backend='gloo')
     assert views['n_gpus'] == 2 and views['scaling'] == 'weak' and views['value'] > 0
     assert 'x2' in views['config']['parallelism']
-    train = _launch(['--workload', 'train', '--steps', '2', '--warmup', '1', '--batch', '2'], n=2, backend='gloo')
+    train = _launch(['--workload', 'train', '--steps', '2', '--warmup', '1', '--batch', '2', '--full'], n=2, backend='gloo')
     assert train['n_gpus'] == 2 and train['value'] > 0
     c = train['config']['collective']
     assert c['backend'] == 'gloo' and c['ms_per_step_without_allreduce'] > 0 and c['exposed_allreduce_wait_ms'] >= 0
     assert c['gradient_dtype_on_the_links'] == 'f32'
-    half = _launch(['--workload', 'train', '--steps', '2', '--warmup', '1', '--batch', '2', '--grad-dtype', 'bf16'], n=2, backend='gloo')
+    half = _launch(['--workload', 'train', '--steps', '2', '--warmup', '1', '--batch', '2', '--grad-dtype', 'bf16', '--full'], n=2, backend='gloo')
     assert half['config']['collective']['gradient_dtype_on_the_links'] == 'bf16' and half['value'] > 0
 
 
@@ -102,7 +102,7 @@ def test_bare_command_starts_its_own_ranks():
     line = json.loads(lines[0])
     assert line['n_gpus'] == 2 and line['config']['ranks'] == 2 and line['config']['backend'] == 'gloo'
     assert line['config']['scenes_per_gpu_per_step'] == 8 and 'x2' in line['config']['parallelism'] and line['value'] > 0
-    r = _bare(['--workload', 'train', '--steps', '2', '--warmup', '1', '--batch', '2'], n=2, backend='gloo')
+    r = _bare(['--workload', 'train', '--steps', '2', '--warmup', '1', '--batch', '2', '--full'], n=2, backend='gloo')
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
     assert line['n_gpus'] == 2 and line['config']['ranks'] == 2 and line['config']['communicator_world_size'] == 2

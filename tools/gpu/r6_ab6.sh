@@ -11,8 +11,8 @@ for l in open('gpurun_out/r6_ab6/ab_gemm_tail.jsonl'):
 PY
 timeout 600 python -m pytest tests/test_hip_bf16.py -q -k "gemm" > $E/tests.log 2>&1; echo "tests rc=$?"; tail -2 $E/tests.log
 for i in 1 2; do
-  timeout 300 python bench.py --workload train --steps 20 --warmup 5 > $E/train_$i.json 2> $E/train_$i.err
-  VF_HIP_LIB=$PWD/viewformer_amd/variants/libvf_g256_r5.so timeout 300 python bench.py --workload train --steps 20 --warmup 5 > $E/train_r5gemm_$i.json 2> $E/train_r5gemm_$i.err
+  timeout 300 python bench.py --workload train --steps 20 --warmup 5 --full > $E/train_$i.json 2> $E/train_$i.err
+  VF_HIP_LIB=$PWD/viewformer_amd/variants/libvf_g256_r5.so timeout 300 python bench.py --workload train --steps 20 --warmup 5 --full > $E/train_r5gemm_$i.json 2> $E/train_r5gemm_$i.err
   python - <<PY
 import json
 for n in ('train_$i','train_r5gemm_$i'):

@@ -14,8 +14,8 @@ timeout 900 python -m pytest tests/test_hip_bf16.py tests/test_train.py tests/te
 for i in 1 2; do
   timeout 300 python bench.py --workload train --steps 20 --warmup 5 > $E/train_$i.json 2> $E/train_$i.err
   VF_HIP_LIB=$PWD/viewformer_amd/variants/libvf_attn_index_order.so timeout 300 python bench.py --workload train --steps 20 --warmup 5 > $E/train_idx_$i.json 2> $E/train_idx_$i.err
-  timeout 300 python bench.py --views 20 --steps 5 --warmup 2 --no-cpu-baseline --no-f32-arm > $E/s20_$i.json 2> $E/s20_$i.err
-  VF_HIP_LIB=$PWD/viewformer_amd/variants/libvf_attn_index_order.so timeout 300 python bench.py --views 20 --steps 5 --warmup 2 --no-cpu-baseline --no-f32-arm > $E/s20_idx_$i.json 2> $E/s20_idx_$i.err
+  timeout 300 python bench.py --views 20 --steps 5 --warmup 2 --full --no-cpu-baseline --no-f32-arm > $E/s20_$i.json 2> $E/s20_$i.err
+  VF_HIP_LIB=$PWD/viewformer_amd/variants/libvf_attn_index_order.so timeout 300 python bench.py --views 20 --steps 5 --warmup 2 --full --no-cpu-baseline --no-f32-arm > $E/s20_idx_$i.json 2> $E/s20_idx_$i.err
   python - <<PY
 import json
 for n in ('train_$i','train_idx_$i'):
