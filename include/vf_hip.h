@@ -300,6 +300,15 @@ int vf_postprocess_u8(const float* x, uint8_t* out, int64_t n, void* stream);
  * [n][Hout][Wout][C]; bilinear = 0: torch 'nearest' (the reference's choice when enlarging), 1: bilinear, align_corners = False
  * (shrinking); through /255, clamp, *255 and a truncating cast exactly as the reference does (bit-identical uint8). */
 int vf_resize_u8(const uint8_t* src, uint8_t* dst, int n_img, int Hin, int Win, int Hout, int Wout, int C, int bilinear, void* stream);
+/* image metrics of the evaluators (viewformer/utils/metrics.py:17-69,164-196; csrc/image_metrics.hip): for each pair of NHWC uint8 images
+ * a[i], b[i] of [n_img][H][W][C], sums[i] = {sum (a-b)^2, sum |a-b|} (exact int64) and ssim[i] = the mean over the (H-6)(W-6)C VALID
+ * positions of the per-pixel SSIM of SSIMMetric (7x7 uniform window, sample covariance, K1 = 1 (sic, :183), K2 = 0.03, data range 1 on
+ * x/255) from exact integer window moments, fp64 ratio.  Deterministic and independent of the batch: per-workgroup partials in
+ * `workspace` (vf_image_metrics_workspace_bytes bytes, 8-byte aligned) reduced in a fixed order by a second launch.  H, W >= 7,
+ * 1 <= C <= 4, n_img >= 1 and non-NULL pointers, else VF_ERR_BAD_ARG before any launch.  The query returns 0 for such shapes. */
+size_t vf_image_metrics_workspace_bytes(int n_img, int H, int W, int C);
+int vf_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n_img, int H, int W, int C, int64_t* sums, double* ssim, void* workspace,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Reduced-precision arm (bf16 MFMA, fp32 activations in HBM, fp32 accumulate / epilogue) for the layers whose

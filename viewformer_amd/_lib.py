@@ -122,6 +122,8 @@ EXPORTS = {
     'vf_argmax_rows_f32': (c_int, [P, c_int64, c_int, c_int, P, P]),
     'vf_postprocess_u8': (c_int, [P, P, c_int64, P]),
     'vf_resize_u8': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'vf_image_metrics_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'vf_image_metrics_u8': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
     # ---- bf16 arm (transformer dense layers, decoder convolutions)
     'vf_gemm_bf16_packed_elems': (c_size_t, [c_int, c_int]),
     'vf_gemm_bf16_pack': (c_int, [P, P, c_int, c_int, c_int64, c_int64, c_int, c_int64, P]),

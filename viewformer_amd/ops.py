@@ -684,3 +684,22 @@ def resize_u8(images, image_size, method=None):
     check(_lib.load().vf_resize_u8(_p(src), _p(out), n, H, W, image_size, image_size, C, 1 if method == 'bilinear' else 0, _stream()),
           'vf_resize_u8')
     return out
+
+
+def image_metrics_u8(a, b):
+    """Per pair of NHWC uint8 images [n,H,W,C] on the GPU (vf_image_metrics_u8): -> (sums int64 [n,2] = {sum (a-b)^2, sum |a-b|}, exact;
+    ssim float64 [n] = mean of the reference's per-pixel SSIM, viewformer/utils/metrics.py:17-69 with K1 = 1 as SSIMMetric calls it, :183).
+    H, W >= 7, C <= 4.  One launch pair, no synchronisation; the values of an image do not depend on the rest of the batch."""
+    if a.shape != b.shape or a.dim() != 4:
+        raise ValueError(f'image_metrics_u8: two [n,H,W,C] batches of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}')
+    a = _chk(a, torch.uint8, 'a').contiguous()
+    b = _chk(b, torch.uint8, 'b').contiguous()
+    n, H, W, C = a.shape
+    if n == 0:
+        return torch.empty((0, 2), dtype=torch.int64, device=a.device), torch.empty(0, dtype=torch.float64, device=a.device)
+    lib = _lib.load()
+    ws =torch.empty(max(int(lib.vf_image_metrics_workspace_bytes(n, H, W, C)), 8), dtype=torch.uint8, device=a.device)
+    sums = torch.empty((n, 2), dtype=torch.int64, device=a.device)
+    ssim = torch.empty(n, dtype=torch.float64, device=a.device)
+    check(lib.vf_image_metrics_u8(_p(a), _p(b), n, H, W, C, _p(sums), _p(ssim), _p(ws), _stream()), 'vf_image_metrics_u8')
+    return sums, ssim
