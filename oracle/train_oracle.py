@@ -248,18 +248,20 @@ class DropoutMasks:
         return torch.cat([old, own], -1)
 
 
-def losses_with_dropout(sd, cfg, poses, tokens, step, rate, seed, dtype=torch.float64, pruned_last_block=True):
+def losses_with_dropout(sd, cfg, poses, tokens, step, rate, seed, dtype=torch.float64, pruned_last_block=True, b0=0):
+    """``b0``: the first scene's index in the global batch (MIGTTrainer.scene_offset)"""
     B, S = tokens.shape[:2]
     L = int(np.prod(tokens.shape[2:]))
     NS = 3 if cfg.use_localization else 2
     pruned = cfg.n_layer - 1 if (pruned_last_block and cfg.n_layer > 0) else None
-    with mg.dropout_masks(DropoutMasks(rate, seed, B, NS, S, L, cfg.d_model, cfg.n_head, dtype, pruned_layer=pruned)):
+    with mg.dropout_masks(DropoutMasks(rate, seed, B, NS, S, L, cfg.d_model, cfg.n_head, dtype, b0=b0, pruned_layer=pruned)):
         return losses(sd, cfg, poses, tokens, step, dtype)
 
 
-def gradients_with_dropout(sd_np, cfg, poses, tokens, step, rate, seed, pruned_last_block=True):
+def gradients_with_dropout(sd_np, cfg, poses, tokens, step, rate, seed, pruned_last_block=True, b0=0):
     sd = {k: torch.tensor(np.asarray(v), dtype=torch.float64, requires_grad=True) for k, v in sd_np.items()}
-    total, metrics = losses_with_dropout(sd, cfg, torch.as_tensor(poses), torch.as_tensor(tokens), step, rate, seed, pruned_last_block=pruned_last_block)
+    total, metrics = losses_with_dropout(sd, cfg, torch.as_tensor(poses), torch.as_tensor(tokens), step, rate, seed, pruned_last_block=pruned_last_block,
+                                         b0=b0)
     total.backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in sd.items()}
     return grads, {k: float(v.detach()) if torch.is_tensor(v) else float(v) for k, v in metrics.items()}

@@ -1538,9 +1538,10 @@ def test_saved_gelu_derivative_forms_of_the_256_tile_kernel(dev, M):
 
 
 @pytest.mark.gpu
-def test_saved_gelu_derivative_training_step_stays_within_the_bf16_arm_bound(dev):
+def test_saved_gelu_derivative_step_plan_stays_within_the_bf16_arm_bound(dev):
     """MIGTTrainer.save_gelu_derivative on / off: the two forms round gelu' at different places (from the fp32 pre-activation once; from the bf16-rounded
-    pre-activation in the backward), so gradients agree to the bf16 arm's own precision, not bit for bit; forward outputs (losses of step 1) are identical."""
+    pre-activation in the backward), so gradients agree to the bf16 arm's own precision, not bit for bit; forward outputs (losses of step 1) are identical.
+    The step's plan (tr.last_plan) records which form it saved and passed to the GELU-backward epilogue."""
     from viewformer_amd.config import MIGTConfig
     from viewformer_amd.migt import MIGT
     from viewformer_amd.train import MIGTTrainer
@@ -1557,7 +1558,7 @@ def test_saved_gelu_derivative_training_step_stays_within_the_bf16_arm_bound(dev
         tr.save_gelu_derivative = flag
         loss = tr.train_step(poses, tokens, apply_update=False)['loss'].clone()
         torch.cuda.synchronize()
-        assert tr._u_is_derivative == flag
+        assert tr.last_plan.gelu_derivative == flag and tr.last_plan.u16 and tr.last_plan.gelu_dual
         res.append((loss, tr.flat_g.clone()))
     assert torch.equal(res[0][0], res[1][0])
     ga, gb = res[0][1].double(), res[1][1].double()

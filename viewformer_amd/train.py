@@ -31,6 +31,7 @@ batch (reduce_sum, :117) while every other term is a batch mean; restated as is.
 """
 import math
 import re
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -127,6 +128,112 @@ def site_resid(i):
 
 def site_mlp(i):
     return 18 + 4 * i
+
+
+def bf16_packed(precision, k, n):
+    """the trainer's rule for a dense layer [k][n] with bf16 packings (MIGTTrainer.repack; it drops the model's other packings)"""
+    return precision == 'bf16' and k % 128 == 0 and n % 128 == 0
+
+
+def block_layer_shapes(cfg):
+    """(k, n) of one transformer block's four dense layers (weights.py)"""
+    d = cfg.d_model
+    return {'attn.c_attn': (d, 3 * d), 'attn.c_proj': (d, d), 'mlp.c_fc': (d, 4 * d), 'mlp.c_proj': (4 * d, d)}
+
+
+def gelu_dual_ok(cfg, M):
+    """c_fc's GELU-dual epilogue at M rows (the 256-tile kernel's limits)"""
+    d = cfg.d_model
+    return M >= 256 and d % 128 == 0 and (4 * d) % 256 == 0 and M * 4 * d * 2 < 2 ** 31
+
+
+# the MIGTTrainer switches step_plan reads (their class values are the defaults)
+PLAN_SWITCHES = ('attention_arith', 'bf16_saved_activations', 'bf16_gradient_operands', 'tn_weight_gradient', 'bf16_residual_gradient',
+                 'fuse_gelu_forward', 'fuse_gelu_backward', 'bf16_preactivation', 'save_gelu_derivative', 'fuse_dropout', 'prune_last_block')
+
+
+class StepPlan(NamedTuple):
+    """what one training step runs (step_plan).  Every flag holds at both row counts the step uses it at: M (the attention, blocks 0 .. n-2)
+    and Mx (the last block from its projection on, ln_f)."""
+    M: int
+    Mx: int                 # M * (NS - 1) / NS with the pruned last block, else M
+    tail: bool              # prune_last_block applies
+    attn16: bool            # attention on the bf16 pipe; bf16 attention output and d(attention output)
+    act16: bool             # LayerNorm outputs / MLP hidden saved as bf16
+    grad16: bool            # bf16 gradient operands: TN weight gradients, 256-tile dX GEMMs
+    res16: bool             # the LayerNorm backward's bf16 copy of the residual-stream gradient (masked there with dropout)
+    drop16: bool            # output dropout in the projection GEMMs' epilogue
+    gelu_dual: bool         # c_fc's GELU-dual epilogue at M
+    gelu_dual_x: bool       # ... at Mx
+    gelu_bwd16: bool        # GELU backward in the epilogue of mlp.c_proj's dX GEMM
+    u16: bool               # where the GELU-dual epilogue runs: the pre-activation saved as bf16
+    gelu_derivative: bool   # ... holding gelu'(u) instead of u
+
+
+def step_plan(cfg, precision, B, S, L, NS, rate=0.0, row0=0, **switches):
+    """the arm decision of MIGTTrainer.train_step for B scenes of S views, L tokens per view, NS streams, dropout ``rate`` and this rank's
+    first row ``row0`` in the global batch — pure host arithmetic on shapes (no device).  ``switches``: PLAN_SWITCHES, default the
+    MIGTTrainer class values.  The last block is pruned only where every fast path the plan turns on at M also holds at Mx."""
+    sw = {k: switches.pop(k, getattr(MIGTTrainer, k)) for k in PLAN_SWITCHES}
+    if switches:
+        raise TypeError(f'step_plan: unknown switches {sorted(switches)}')
+    d, H = cfg.d_model, cfg.n_head
+    Tn, M = NS * S * L, B * NS * S * L
+    shapes = block_layer_shapes(cfg)
+    p16 = {n: bf16_packed(precision, k, n_) for n, (k, n_) in shapes.items()}
+    # attention of the bf16 arm on the bf16 matrix pipe (csrc/attention_dma.hip + attention_train_bf16.hip) where its kernels apply:
+    # 64-token views, the wide c_attn / c_proj layers on their bf16 packings; otherwise the exact-f32 kernels.  Attention dropout is
+    # inside both sets of kernels (the same masks)
+    attn = (sw['attention_arith'] == 'bf16' and precision == 'bf16' and T.attn_bf16_supported(Tn, L) and d // H == 64
+            and p16['attn.c_attn'] and p16['attn.c_proj'] and (rate == 0.0 or Tn * (Tn // 4) < 2 ** 32))
+    # bf16 arm, wide layers: the activations only GEMMs read — both LayerNorm outputs, the attention output, the MLP hidden — are
+    # SAVED AS bf16 by their producers (the rounding the GEMM applied on load before: identical products), so the forward GEMMs take
+    # the 256-tile LDS-DMA kernel (bf16 A operand) and the saved activations halve; the backward reads them through the widening
+    # transpose (dW) and never otherwise (LayerNorm / GELU backward use the fp32 h / u)
+    act = attn and sw['bf16_saved_activations'] and p16['mlp.c_fc'] and p16['mlp.c_proj']
+
+    def at(R, r0):
+        """the fast paths R rows (the first of them row r0 of the global batch) can take"""
+        # a bf16 operand of a backward GEMM needs the bf16 arm of _linear_bwd / _linear_dx: R % 128 == 0
+        attn16 = attn and R % 128 == 0
+        act16 = act and R % 128 == 0
+        # ... and the two gradients only GEMMs read — d(MLP pre-activation) from the GELU backward, d(q | k | v) from the attention backward —
+        # are WRITTEN as bf16 by those kernels (again the rounding their consumers applied on load: identical dX / dW; the bias gradients
+        # become sums of the rounded values), so that dX takes the 256-tile kernel and the TN kernel moves half the bytes.  That needs every
+        # consumer that can read one: the TN weight-gradient kernel for all four layer shapes of a block (K, N multiples of 256, 32-bit
+        # offsets) and the 256-tile GEMM for the dX products (an explicit predicate: d_model 384 or 640 passes the packing rule of `act16`
+        # but not these, and keeps fp32 gradients + the transpose / pack weight-gradient path)
+        grad16 = (act16 and sw['bf16_gradient_operands'] and sw['tn_weight_gradient']
+                  and all(ops.gemm_tn_bf16_shape_ok(R, k, n) and ops.gemm_g256_shape_ok(R, n, k) for k, n in shapes.values()))
+        # the LayerNorm backward hands the projection layers' backward GEMMs a bf16 copy of the residual-stream gradient (with dropout: under
+        # the consuming layer's output mask, which only the fused form applies there).  With dropout the masks ride in layernorm_bwd(drop=...),
+        # which indexes 32-bit mask groups: the same bound gemm_drop_supported puts on the forward — a global batch so large that
+        # (R + r0) / 4 * d passes 2^32 falls back to the dropout_add passes instead of raising
+        res16 = (grad16 and sw['bf16_residual_gradient'] and sw['fuse_gelu_backward']
+                 and (rate == 0.0 or (sw['fuse_dropout'] and r0 % 4 == 0 and ((R + r0 + 3) // 4) * d < 2 ** 32)))
+        # residual / MLP dropout in the projection GEMM's epilogue (False: GEMM, then the dropout_add pass: the same masks)
+        drop16 = (bool(rate) and sw['fuse_dropout'] and attn16
+                  and all(ops.gemm_drop_supported(R, *shapes[n], r0) for n in ('attn.c_proj', 'mlp.c_proj')))
+        dual = act16 and sw['fuse_gelu_forward'] and gelu_dual_ok(cfg, R)
+        return dict(attn16=attn16, act16=act16, grad16=grad16, res16=res16, drop16=drop16, gelu_dual=dual)
+
+    here = at(M, row0)
+    # prune_last_block: the losses read the branch streams only (MASK -> LM head, LOC -> pose head: migt.py:416-448); every block but the last
+    # needs the main stream's rows as keys and values of the next one, the LAST block's projection / LayerNorm / MLP on them feed nothing (see
+    # train_step).  Mx = B (NS - 1) S L rows need not tile like M: with NS = 2 and an odd B * S, Mx % 128 == 64; with B * S = 2, Mx = 128 is
+    # under the 256-tile kernels' minimum.  The step is pruned only where the plan taken at M holds at Mx as well
+    tail = bool(sw['prune_last_block'] and NS > 1 and cfg.n_layer > 0)
+    if tail:
+        there = at(B * (NS - 1) * S * L, row0 // NS * (NS - 1))
+        tail = all(there[k] for k, on in here.items() if on)
+    Mx = B * (NS - 1) * S * L if tail else M
+    # the pre-activation saved as bf16: its only reader then is the GELU-backward epilogue of the 256-tile kernel, fed by the bf16
+    # residual-stream gradient
+    u16 = here['res16'] and sw['bf16_preactivation']
+    return StepPlan(M=M, Mx=Mx, tail=tail, attn16=here['attn16'], act16=here['act16'], grad16=here['grad16'], res16=here['res16'],
+                    drop16=here['drop16'], gelu_dual=here['gelu_dual'],
+                    gelu_dual_x=here['act16'] and sw['fuse_gelu_forward'] and gelu_dual_ok(cfg, Mx),
+                    gelu_bwd16=here['grad16'] and sw['fuse_gelu_backward'], u16=u16, gelu_derivative=u16 and sw['save_gelu_derivative'])
 
 
 class MIGTTrainer:
@@ -251,7 +358,7 @@ class MIGTTrainer:
         pack_items, pack_names = [], []
         for name, dn in m._dense.items():
             k32 = dn.k % 32 == 0
-            to16 = bf16 and k32 and dn.k % 128 == 0 and dn.n % 128 == 0
+            to16 = bf16_packed(m.precision, dn.k, dn.n)
             to6 = x6 and k32 and dn.k % 64 == 0 and dn.n % 64 == 0
             # the native-f32 packings are refreshed only where no faster arm applies (they were 477 pack launches per step that nothing
             # read: the wide layers run on their bf16 / split packings); the transposed native packing of a wide layer is built on demand
@@ -318,21 +425,23 @@ class MIGTTrainer:
     fuse_dropout = True               # bf16 arm: residual / MLP dropout in the projection GEMM's epilogue and in the LayerNorm backward's bf16 copy
                                       # (False: the separate dropout_add passes; the same masks, the same values up to the GEMM's own rounding)
 
-    def _proj_dropout(self, x, name, M, res, drop):
-        """res + dropout(x @ W + b)  (attn.c_proj -> resid_dropout, migt.py:216; mlp.c_proj -> the MLP's dropout, :72)"""
+    def _proj_dropout(self, x, name, M, res, drop, fused=False):
+        """res + dropout(x @ W + b)  (attn.c_proj -> resid_dropout, migt.py:216; mlp.c_proj -> the MLP's dropout, :72).  ``fused``
+        (StepPlan.drop16): the mask in the GEMM's epilogue, for a bf16 ``x``"""
         dn = self.model._dense[name]
         if not drop[0]:
             return self._linear(x, name, M, res=res)
-        if (self.fuse_dropout and dn.wp16 is not None and x.dtype == torch.bfloat16 and ops.gemm_drop_supported(M, dn.k, dn.n, drop[3])):
+        if fused and x.dtype == torch.bfloat16:
             out = torch.empty((M, dn.n), dtype=torch.float32, device=x.device)
             ops.igemm(x, dn.wp16, M, dn.k, dn.n, out, bias=dn.bias, res=res, bf16=True, a16=True, drop=drop)
             return out
         y = self._linear(x, name, M)
         return T.dropout_add(y, drop[0], drop[1], drop[2], res=res, out=y, row0=drop[3])
 
-    def _linear_bwd(self, name, x, dy, M, need_dx=True, res=None, dx_bf16=False, gelu_bwd_u=None):
+    def _linear_bwd(self, name, x, dy, M, need_dx=True, res=None, dx_bf16=False, gelu_bwd_u=None, u_is_derivative=False):
         """grads of y = x @ W + b given dy [M,N]; returns dx (+res) or None.  ``x`` may be a saved bf16 activation (bf16 arm);
-        ``dx_bf16``: the bf16 arm's dX GEMM writes bf16 (the attention backward's dO operand)."""
+        ``dx_bf16``: the bf16 arm's dX GEMM writes bf16 (the attention backward's dO operand); ``gelu_bwd_u``, ``u_is_derivative``: see
+        _linear_dx."""
         dn = self.model._dense[name]
         K, N = dn.k, dn.n
         bf16 = name in self.wpT16 and dn.wp16 is not None and M % 128 == 0
@@ -357,7 +466,7 @@ class MIGTTrainer:
                 # (alone on the compute stream the launch takes the full-machine split, another summation order; serial_wgrad_split_as_overlapped
                 # keeps the second stream's split, for bit-for-bit comparisons of the two modes)
                 ops.gemm_tn_bf16(x, dy, M, K, N, gw, gb, accumulate=not first, beside_another_gemm=self.serial_wgrad_split_as_overlapped and need_dx)
-            return self._linear_dx(name, dy, M, res, dx_bf16, gelu_bwd_u) if need_dx else None
+            return self._linear_dx(name, dy, M, res, dx_bf16, gelu_bwd_u, u_is_derivative) if need_dx else None
         if dy.dtype != torch.float32:
             raise RuntimeError('a bf16 gradient operand needs the TN weight-gradient path')
         if first:                                          # the paths below accumulate
@@ -394,7 +503,7 @@ class MIGTTrainer:
             ops.igemm(xt, dyp, K, Mp, N, gw, res=gw, lda=Mp)                         # dW += X^T dY
         if not need_dx:
             return None
-        return self._linear_dx(name, dy, M, res, dx_bf16, gelu_bwd_u)
+        return self._linear_dx(name, dy, M, res, dx_bf16, gelu_bwd_u, u_is_derivative)
 
     serial_wgrad_split_as_overlapped = False
     overlap_weight_gradients = True   # bf16 arm: the TN weight-gradient GEMM of a layer on a second stream beside that layer's dX GEMM
@@ -470,9 +579,10 @@ class MIGTTrainer:
             torch.cuda.current_stream(self.dev).wait_stream(self._side_stream)
             self._side_busy = False
 
-    def _linear_dx(self, name, dy, M, res=None, dx_bf16=False, gelu_bwd_u=None):
-        """dx = dy @ W^T (+ res).  ``gelu_bwd_u`` (bf16 arm): the saved fp32 pre-activation u of the GELU that produced this layer's input —
-        the GEMM's epilogue then returns bf16(dx * gelu'(u)), the GELU backward without the fp32 dx ever reaching HBM"""
+    def _linear_dx(self, name, dy, M, res=None, dx_bf16=False, gelu_bwd_u=None, u_is_derivative=False):
+        """dx = dy @ W^T (+ res).  ``gelu_bwd_u`` (bf16 arm): the saved pre-activation u of the GELU that produced this layer's input —
+        the GEMM's epilogue then returns bf16(dx * gelu'(u)), the GELU backward without the fp32 dx ever reaching HBM.  ``u_is_derivative``
+        (save_gelu_derivative): that bf16 tensor holds gelu'(u) already"""
         dn = self.model._dense[name]
         K, N = dn.k, dn.n
         x6 = name in self.wpT6 and dn.wp6 is not None and M % 64 == 0
@@ -485,7 +595,7 @@ class MIGTTrainer:
                 raise RuntimeError('the fused GELU backward needs the bf16 arm, a bf16 result and no residual')
             u16 = gelu_bwd_u.dtype == torch.bfloat16
             ops.igemm(dy, self.wpT16[name], M, N, K, dx, res=gelu_bwd_u, epilogue=ops.EPI_GELU_BWD, bf16=True, a16=dy.dtype == torch.bfloat16, o16=True,
-                      res16=u16, gelu_grad=u16 and self._u_is_derivative)       # (save_gelu_derivative: the tensor holds gelu'(u) already)
+                      res16=u16, gelu_grad=u16 and u_is_derivative)
         elif bf16:
             ops.igemm(dy, self.wpT16[name], M, N, K, dx, res=res, bf16=True, a16=dy.dtype == torch.bfloat16, o16=dx_bf16)   # (bf16 dY: the 256-tile kernel)
         elif x6:
@@ -551,13 +661,8 @@ class MIGTTrainer:
                                       # mlp.c_proj dX GEMM — then multiplies by a loaded value instead of evaluating erf + exp per element again (that epilogue
                                       # was 22 us of a 148 us launch).  gelu' is taken from the fp32 pre-activation and rounded once; before it was evaluated
                                       # on the bf16-rounded u
-    _u_is_derivative = False
     fuse_gelu_forward = True          # bf16 arm: c_fc writes u (fp32, saved) and bf16 gelu(u) from one epilogue (VF_EPI_GELU_DUAL); the GELU there
                                       # is the inference arm's vf_gelu_erf_fast (|err| 1.5e-7: a few outputs round to the neighbouring bf16)
-
-    def _gelu_dual_ok(self, M):
-        c = self.cfg
-        return M >= 256 and c.d_model % 128 == 0 and (4 * c.d_model) % 256 == 0 and M * 4 * c.d_model * 2 < 2 ** 31   # (the 256-tile kernel's limits)
 
     bf16_residual_gradient = True     # bf16 arm: the LayerNorm backward also writes its result as bf16 — the operand of the two projection
                                       # layers' backward GEMMs, which then run on the 256-tile kernel (the rounding is the one the GEMM's operand
@@ -643,6 +748,12 @@ class MIGTTrainer:
         return dqkv
 
     # ------------------------------------------------------------------ the step
+    last_plan = None                  # the StepPlan of the last train_step call
+
+    def plan(self, B, S, L, NS, rate=0.0, row0=0):
+        """step_plan with this trainer's config, precision and switches"""
+        return step_plan(self.cfg, self.model.precision, B, S, L, NS, rate, row0, **{k: getattr(self, k) for k in PLAN_SWITCHES})
+
     def train_step(self, poses, tokens, reduce_gradients: bool = True, apply_update: bool = True, _forward_only: bool = False):
         """poses [b,S,7] float32 (already through process_batch: relative + normalised), tokens [b,S,t,t] int.
         Returns the metrics dict of MIGT.train_step (loss, ce_loss, acc, pose_* ...).  ``_forward_only`` (test_step / predict_step):
@@ -696,33 +807,10 @@ class MIGTTrainer:
         if rate:
             T.dropout_add(h, rate, seed, SITE_EMBED, out=h, row0=row0)               # self.drop, migt.py:403
         saved = []
-        # attention of the bf16 arm on the bf16 matrix pipe (csrc/attention_dma.hip + attention_train_bf16.hip) where its kernels apply:
-        # 64-token views, the wide c_attn / c_proj layers on their bf16 packings; otherwise the exact-f32 kernels.  Attention dropout is
-        # inside both sets of kernels (the same masks)
-        ca, cp = m._dense['h.0.attn.c_attn'], m._dense['h.0.attn.c_proj']
-        attn16 = (self.attention_arith == 'bf16' and m.precision == 'bf16' and T.attn_bf16_supported(Tn, L)
-                  and d // H == 64 and ca.wp16 is not None and cp.wp16 is not None and M % 128 == 0
-                  and (rate == 0.0 or Tn * (Tn // 4) < 2 ** 32))
-        # bf16 arm, wide layers: the activations only GEMMs read — both LayerNorm outputs, the attention output, the MLP hidden — are
-        # SAVED AS bf16 by their producers (the rounding the GEMM applied on load before: identical products), so the forward GEMMs take
-        # the 256-tile LDS-DMA kernel (bf16 A operand) and the saved activations halve; the backward reads them through the widening
-        # transpose (dW) and never otherwise (LayerNorm / GELU backward use the fp32 h / u)
-        # ... and the two gradients only GEMMs read — d(MLP pre-activation) from the GELU backward, d(q | k | v) from the attention backward —
-        # are WRITTEN as bf16 by those kernels (again the rounding their consumers applied on load: identical dX / dW; the bias gradients
-        # become sums of the rounded values), so that dX takes the 256-tile kernel and the TN kernel moves half the bytes
-        act16 = attn16 and self.bf16_saved_activations and all(m._dense[f'h.0.{n}'].wp16 is not None for n in ('mlp.c_fc', 'mlp.c_proj'))
-        # bf16 gradient operands need every consumer that can read one: the TN weight-gradient kernel for all four layer shapes of a block
-        # at this M (K, N multiples of 256, 32-bit offsets) and the 256-tile GEMM for the dX products (an explicit predicate: d_model 384
-        # or 640 passes the packing rule of `act16` but not these, and keeps fp32 gradients + the transpose / pack weight-gradient path)
-        block_shapes = [(m._dense[f'h.0.{n}'].k, m._dense[f'h.0.{n}'].n) for n in ('attn.c_attn', 'attn.c_proj', 'mlp.c_fc', 'mlp.c_proj')]
-        grad16 = (act16 and self.bf16_gradient_operands and self.tn_weight_gradient
-                  and all(ops.gemm_tn_bf16_shape_ok(M, k_, n_) and ops.gemm_g256_shape_ok(M, n_, k_) for k_, n_ in block_shapes))
-        # the LayerNorm backward hands the projection layers' backward GEMMs a bf16 copy of the residual-stream gradient (with dropout: under
-        # the consuming layer's output mask, which only the fused form applies there)
-        # (with dropout the masks ride in layernorm_bwd(drop=...), which indexes 32-bit mask groups: the same bound gemm_drop_supported puts on the
-        # forward — a global batch so large that (M + row0) / 4 * d passes 2^32 falls back to the dropout_add passes instead of raising)
-        res16 = (grad16 and self.bf16_residual_gradient and self.fuse_gelu_backward
-                 and (rate == 0.0 or (self.fuse_dropout and row0 % 4 == 0 and ((M + row0 + 3) // 4) * d < 2 ** 32)))
+        # the bf16 arm's fast paths and the pruned last block: one decision from the shapes, valid at every row count it is used at (step_plan)
+        plan = self.plan(B, S, L, NS, rate, row0)
+        self.last_plan = plan
+        attn16, act16, grad16, res16 = plan.attn16, plan.act16, plan.grad16, plan.res16
         drop_of = lambda site: (rate, seed, site, row0)                              # noqa: E731  (elementwise sites: row offset)
         drop_attn = lambda i_: (rate, seed, site_attn(i_), plane0)                   # noqa: E731  (attention: plane offset)
         # prune_last_block: the losses read the branch streams only (MASK -> LM head, LOC -> pose head: migt.py:416-448); every block but the last needs
@@ -731,8 +819,7 @@ class MIGTTrainer:
         # they are contiguous per scene), ln_f with them; the attention backward and everything below it get the two gradients scattered back with
         # zeros in the main stream's rows, which is what they were.  The dropout masks of the last block's two sites are indexed by the gathered rows
         nb = NS - 1
-        tail = bool(self.prune_last_block and NS > 1 and c.n_layer > 0)
-        Mx = B * nb * S * L if tail else M                                           # rows from the last block's projection on
+        tail, Mx = plan.tail, plan.Mx                                                # Mx: rows from the last block's projection on
         drop_x = (lambda site: (rate, seed, site, row0 // NS * nb)) if tail else drop_of      # noqa: E731
         for i in range(c.n_layer):
             p = f'h.{i}'
@@ -755,23 +842,22 @@ class MIGTTrainer:
             if last:
                 att_i = att.view(B, NS, S * L, att.shape[-1])[:, 1:].reshape(Mx, att.shape[-1])
                 h_i = h.view(B, NS, S * L, d)[:, 1:].reshape(Mx, d)
-            h_mid = self._proj_dropout(att_i, p + '.attn.c_proj', Mi, h_i, drop_i(site_resid(i)))      # h + resid_dropout(c_proj(a)), migt.py:216,233
+            h_mid = self._proj_dropout(att_i, p + '.attn.c_proj', Mi, h_i, drop_i(site_resid(i)), plan.drop16)    # h + resid_dropout(c_proj(a)), migt.py:216,233
             n2 = ops.layernorm(h_mid, *m._ln[p + '.ln_2'], Mi, d, out_bf16=act16)
-            if act16 and self.fuse_gelu_forward and self._gelu_dual_ok(Mi):
-                # c_fc keeps the fp32 pre-activation for the backward pass AND hands bf16 gelu(u) to mlp.c_proj from one epilogue
+            if plan.gelu_dual_x if last else plan.gelu_dual:
+                # c_fc keeps the pre-activation for the backward pass AND hands bf16 gelu(u) to mlp.c_proj from one epilogue
                 dn = m._dense[p + '.mlp.c_fc']
-                u16 = res16 and self.bf16_preactivation      # (its only reader then: the
-                # GELU-backward epilogue of the 256-tile kernel, fed by the bf16 residual-stream gradient)
+                u16 = plan.u16
                 u = torch.empty((Mi, dn.n), dtype=torch.bfloat16 if u16 else torch.float32, device=dev)
                 f = torch.empty((Mi, dn.n), dtype=torch.bfloat16, device=dev)
-                u_deriv = bool(u16 and self.save_gelu_derivative)                         # (`u` then holds gelu'(u): see save_gelu_derivative)
+                u_deriv = plan.gelu_derivative                                            # (`u` then holds gelu'(u): see save_gelu_derivative)
                 ops.igemm(n2, dn.wp16, Mi, dn.k, dn.n, u, bias=dn.bias, epilogue=ops.EPI_GELU_DUAL, bf16=True, a16=True, o16=u16, out_aux=f,
                           gelu_grad=u_deriv)
             else:
                 u_deriv = False
                 u = self._linear(n2, p + '.mlp.c_fc', Mi)
                 f = T.gelu(u, out_bf16=act16)
-            h_out = self._proj_dropout(f, p + '.mlp.c_proj', Mi, h_mid, drop_i(site_mlp(i)))           # h + dropout(mlp(...)), migt.py:72,237
+            h_out = self._proj_dropout(f, p + '.mlp.c_proj', Mi, h_mid, drop_i(site_mlp(i)), plan.drop16)         # h + dropout(mlp(...)), migt.py:72,237
             if not _forward_only:
                 saved.append((h, n1, qkv, att, att_i, h_mid, n2, u, f, lse, u_deriv))
             h = h_out
@@ -852,9 +938,11 @@ class MIGTTrainer:
                                      out=getattr(self, 'lm_T', None))                 # step: a packing cached from step 1 would be silently stale)
                 self._lm_T_stale = False
             ops.igemm(dlogits, self.lm_T, M1, nE, d, dhm)
-            dlt = T.transpose(dlogits, M1, nE)
-            hp = ops.pack(hmask, M1, d, 1, sk=d, sn=1, st=0)
-            ops.igemm(dlt, hp, nE, M1, d, gwte)                                       # rows [0, nE) of the (zeroed) grad
+            M1p = (M1 + 31) // 32 * 32                                                # reduction length padded to the K stage (B * S * L = 48 at
+            dlt = T.transpose(dlogits, M1, nE, ld_dst=M1p,                            # 16-token views and an odd B * S)
+                              out=torch.zeros((1, nE, M1p), dtype=torch.float32, device=dev) if M1p != M1 else None)
+            hp = ops.pack(hmask, M1, d, 1, sk=d, sn=1, st=0)                          # rows >= M1 are zero-filled by the packer
+            ops.igemm(dlt, hp, nE, M1p, d, gwte, lda=M1p)                             # rows [0, nE) of the (zeroed) grad
         dhf[:, 1 - so] = dhm.view(B, S, L, d)
         if use_loc:
             name = 'pose_criterion.pose_classifier.c_proj'
@@ -885,12 +973,12 @@ class MIGTTrainer:
                  and (self._world() == 1 or not reduce_gradients or (overlap and self.grad_allreduce_dtype == 'f32')))
         for i in reversed(range(c.n_layer)):
             p = f'h.{i}'
-            h_in, n1, qkv, att, att_i, h_mid, n2, u, f, lse, self._u_is_derivative = saved[i]
+            h_in, n1, qkv, att, att_i, h_mid, n2, u, f, lse, u_deriv = saved[i]
             last = tail and i == c.n_layer - 1
             Mi, drop_i = (Mx, drop_x) if last else (M, drop_of)
             dy_mlp = dh16 if res16 else (T.dropout_add(dh, rate, seed, site_mlp(i), row0=drop_i(0)[3]) if rate else dh)      # d(mlp.c_proj output)
-            if grad16 and self.fuse_gelu_backward:                                   # GELU backward in the epilogue of the dX GEMM that feeds it
-                du = self._linear_bwd(p + '.mlp.c_proj', f, dy_mlp, Mi, dx_bf16=True, gelu_bwd_u=u)
+            if plan.gelu_bwd16:                                                      # GELU backward in the epilogue of the dX GEMM that feeds it
+                du = self._linear_bwd(p + '.mlp.c_proj', f, dy_mlp, Mi, dx_bf16=True, gelu_bwd_u=u, u_is_derivative=u_deriv)
             else:
                 df = self._linear_bwd(p + '.mlp.c_proj', f, dy_mlp, Mi)
                 du = T.gelu_bwd(u, df, out_bf16=grad16)
