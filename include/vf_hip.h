@@ -43,8 +43,9 @@ int vf_abi_version(void);                 /* bumps when a signature changes */
 size_t vf_sizeof_igemm_args(void);        /* sizeof(vf_igemm_args) / sizeof(vf_pack_desc) as this library was built: a binding compares */
 size_t vf_sizeof_pack_desc(void);         /* its mirror of the two structs with them before the first call */
 const char* vf_build_arch(void);          /* "gfx950" */
-/* developer switches compiled into this library (ablation / cycle-stamp builds of the kernels, csrc/vf_common.h): the count and
- * the i-th macro name.  A product build returns 0; tests/test_abi.py asserts it of the shipped library. */
+/* developer switches compiled into this library (csrc/vf_common.h: VF_X_TRINTRIN, the compiler-ordered reference build that
+ * tests/test_hip_ring_stress.py compares with): the count and the i-th macro name.  A product build returns 0; tests/test_abi.py asserts
+ * it of the shipped library. */
 int vf_build_flags(void);
 const char* vf_build_flag_name(int i);
 /* Kernel selection for A/B runs and parity tests.  The library reads NO environment variable; the only run-time switches are these, and each

@@ -75,20 +75,24 @@ def test_adamw_pack_table_validation_is_host_side(lib):
 
 
 def test_shipped_library_has_no_developer_switch_compiled_in(lib):
-    """The kernel sources keep ablation / cycle-stamp switches (-DADMA_X_NOCOMPUTE, -DATT_X_NOMFMA, -DG256_STAMPS, ...) for the
-    experiments under tools/; a translation unit built with one registers its name (csrc/vf_common.h).  The product library must
-    register none — and the registry itself must work (the variant builds under tools/ rely on it to label their output)."""
+    """The kernel sources hold no compile-time knobs: the one developer switch left, -DVF_X_TRINTRIN (the compiler-ordered reference
+    build of the DMA-ring kernels that tests/test_hip_ring_stress.py compares with), registers its name when a translation unit is built
+    with it (csrc/vf_common.h).  The product library must register none, and every macro that a preprocessor conditional in csrc/ tests
+    must be such a registered switch, so that no unregistered knob with a default can select a path no build or test exercises."""
     names = [lib.vf_build_flag_name(i) for i in range(lib.vf_build_flags())]
     assert lib.vf_build_flags() == 0, f'libvf_hip.so was built with developer switches: {names}'
     assert lib.vf_build_flag_name(0) is None
-    # every switch the sources test for is one the registry knows (a new ablation macro must be added to vf_common.h's list)
     csrc = os.path.join(REPO, 'viewformer_amd', 'csrc')
-    known = set(re.findall(r'VF_REG_FLAG\((\w+)\)', open(os.path.join(csrc, 'vf_common.h')).read()))
-    used = set()
-    for f in os.listdir(csrc):
+    known = set(re.findall(r'^VF_REG_FLAG\((\w+)\)', open(os.path.join(csrc, 'vf_common.h')).read(), flags=re.M))
+    used = {}
+    for f in sorted(os.listdir(csrc)):
         if f.endswith(('.hip', '.h')):
-            used |= set(re.findall(r'#\s*if(?:def|ndef)?\s+(?:!\s*)?(?:defined\s*\(\s*)?(\w+_X_\w+|\w+_STAMPS|\w+_CLOCKPROBE|\w+_VIA_REGS)', open(os.path.join(csrc, f)).read()))
-    assert used <= known, used - known
+            src = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(csrc, f)).read(), flags=re.S).replace('\\\n', ' ')
+            for cond in re.findall(r'^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$', src, flags=re.M):
+                for name in re.findall(r'\b[A-Za-z_]\w*\b', cond.split('//')[0]):
+                    if name != 'defined':
+                        used.setdefault(name, f)
+    assert {n: f for n, f in used.items() if n not in known} == {}
 
 
 def test_library_reads_no_environment_and_its_switches_are_explicit(lib):

@@ -357,8 +357,9 @@ def test_attention_dma_32_query_waves_are_bit_identical_to_64_query_waves(dev, B
     assert torch.equal(res[1][0], res[1][1]) and torch.equal(res[1][2], res[1][4])      # (the lse output changes nothing; dropout does not touch it)
 
 
-# (The bit-identity tests of round 3's three slower forms of this kernel — 8-wave, resident, software-pipelined — left with the kernels:
-# tools/variants/attention_dma_r3_records.hip; they passed on MI355X at commit 7e8c4c4, GPUTEST_r03.json.)
+# (The bit-identity tests of round 3's three slower forms of this kernel — 8-wave, resident, software-pipelined — left with the kernels,
+# whose sources were last kept in tools/variants/attention_dma_r3_records.hip at commit 9158f1d; they passed on MI355X at commit 7e8c4c4,
+# GPUTEST_r03.json.)
 
 
 def test_bf16_activation_chain_is_bit_identical(dev):

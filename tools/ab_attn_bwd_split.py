@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """In-process A/B of the bf16 training attention backward, the dQ launch and the dK / dV launch timed SEPARATELY, across builds of libvf_hip.so at the
-training step's shape (10 scenes x 12 heads x 3 streams x 10 views), dropout 0 and 0.1, alternated.  Timing only (ablation builds give wrong results);
-with AB_CHECK=1 every build's dq / dk / dv is compared with the first build's.  usage: python tools/ab_attn_bwd_split.py lib1.so lib2.so ..."""
+training step's shape (10 scenes x 12 heads x 3 streams x 10 views), dropout 0 and 0.1, alternated.  With AB_CHECK=1 every build's dq / dk / dv
+is compared with the first build's.  usage: python tools/ab_attn_bwd_split.py lib1.so lib2.so ..."""
 import json
 import os
 import statistics

@@ -9,7 +9,7 @@ import os
 from ctypes import c_int, c_int32, c_int64, c_float, c_void_p, c_size_t, c_char_p, POINTER
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# VF_HIP_LIB: developer override used by tools/variants.sh to time side-by-side builds of the same ABI
+# VF_HIP_LIB: developer override that runs a whole process (bench.py, tools/microbench.py) on another build of the same ABI, for A/B timing
 LIB_PATH = os.environ.get('VF_HIP_LIB') or os.path.join(HERE, 'libvf_hip.so')
 
 

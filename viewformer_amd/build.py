@@ -67,43 +67,6 @@ VARIANTS = {
     # hipcc then orders them behind the ring with its own `s_waitcnt vmcnt(0)` — the slow but compiler-ordered reference of
     # tests/test_hip_ring_stress.py, which compares the two builds' results bit for bit
     'trintrin': (['-DVF_X_TRINTRIN'], ['attention_dma', 'attention_train_bf16', 'gemm_tn_bf16']),
-    # A/B only (tools/ab_inprocess_*attn.py): the attention launches' owner blocks in index order instead of heaviest first
-    'attn_index_order': (['-DADMA_HEAVY_FIRST=0', '-DATB_HEAVY_FIRST=0'], ['attention_dma', 'attention_train_bf16']),
-    # A/B only: the x3h16 convolution's staging transform (GroupNorm-apply + swish + fp16 split) on packed fp32 instructions (bit-identical, slower)
-    'x3h16_pk_xform': (['-DX3H16_PKXFORM=1'], ['conv3_halo_x3h']),
-    # A/B only: rows per block of the LayerNorm backward (16 shipped)
-    'ln_bwd_rpb8': (['-DVF_LN_BWD_RPB=8'], ['train_ops']),
-    'ln_bwd_rpb32': (['-DVF_LN_BWD_RPB=32'], ['train_ops']),
-    # A/B only: the dQ kernel with a two-slot ring (48 KB: three workgroups per CU instead of two, one tile ahead instead of two)
-    'dq_ring2': (['-DATB_DQ_RING=2'], ['attention_train_bf16']),
-    # A/B only: the dK / dV kernel's dropout words hashed by every lane (one per score) instead of once per lane quad (same words, same masks)
-    # ablations of the backward attention kernels (results WRONG; timing only): no "tr" image DMAs / no tile compute / no tile DMAs
-    'atb_abl1': (['-DATB_ABL=1'], ['attention_train_bf16']),
-    'atb_abl2': (['-DATB_ABL=2'], ['attention_train_bf16']),
-    'atb_abl4': (['-DATB_ABL=4'], ['attention_train_bf16']),
-    'atb_abl9': (['-DATB_ABL=9'], ['attention_train_bf16']),
-    'atb_abl6': (['-DATB_ABL=6'], ['attention_train_bf16']),
-    'atb_abl6': (['-DATB_ABL=6'], ['attention_train_bf16']),
-    # A/B only: the dK / dV kernel's mask rotation as shl / shr / or (before the third session of round 6)
-    'dkv_rot3': (['-DVF_X_DKV_ROT3'], ['attention_train_bf16']),
-    # A/B only: the dK / dV kernel with a rows image AND a tr image per streamed operand, ring of 2, two workgroups per CU (before the third session of round 6)
-    'dkv_two_images': (['-DATB_KV_UNI=0'], ['attention_train_bf16']),
-    # A/B only: the dQ kernel with K rows | V rows | K tr per slot (72 KB ring, two workgroups per CU)
-    'dq_three_images': (['-DATB_DQ_UNI=0'], ['attention_train_bf16']),
-    'dq_ring4': (['-DATB_DQ_RING=4'], ['attention_train_bf16']),
-    # A/B only: both backward attention kernels as before the third session of round 6 (separate rows / tr images, two workgroups per CU, shl / shr / or rotation)
-    'atb_session2': (['-DATB_KV_UNI=0', '-DATB_DQ_UNI=0', '-DVF_X_DKV_ROT3'], ['attention_train_bf16']),
-    # A/B only: the forward DMA-ring attention with a three-slot ring (48 KB: three workgroups per CU, two tiles in flight)
-    'adma_ring3': (['-DADMA_RING=3'], ['attention_dma']),
-    'dkv_sel2': (['-DVF_X_DKV_SEL2'], ['attention_train_bf16']),
-    # A/B only: the forward DMA-ring attention with four CONSECUTIVE query views per workgroup under the streams mask too
-    'adma_consecutive': (['-DADMA_REGROUP=0'], ['attention_dma']),
-    # A/B only: the backward attention kernels' tile lists from loops over visible() (integer divisions) instead of closed-form bit masks
-    'atb_visloop': (['-DVF_X_ATB_VISLOOP'], ['attention_train_bf16']),
-    # ablations of the forward DMA-ring kernel (results WRONG; timing only)
-    'adma_nocompute': (['-DADMA_X_NOCOMPUTE'], ['attention_dma']),
-    'adma_skeleton': (['-DADMA_X_NOCOMPUTE', '-DADMA_X_NODMA'], ['attention_dma']),
-    'dkv_hash_per_element': (['-DVF_X_DKV_HASH_PER_ELEMENT'], ['attention_train_bf16']),
 }
 
 

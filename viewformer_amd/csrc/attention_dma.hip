@@ -3,7 +3,7 @@
 // Semantics of attention_lp.hip MODE 0 (S^T = K.Q^T on v_mfma_f32_32x32x16_bf16, fp32 online softmax, probabilities rounded to bf16,
 // O^T += V^T.P^T; viewformer/models/branching_attention.py:5-18,41-61,82-126), but the operands never pass through VGPRs on their way in.
 // attention_lp.hip at the bench shape (128 scenes x 12 heads x 512 tokens) spends its time waiting for memory, not computing: removing its
-// MFMAs or its softmax changes nothing (239 -> 224 us), removing the K / V tile loads gives 155 us (ablation builds, tools/variants.sh).
+// MFMAs or its softmax changes nothing (239 -> 224 us), removing the K / V tile loads gives 155 us (ablation builds).
 // Per CU the deliverable load bandwidth is set by the bytes in flight (L2 latency x ~16 B/clk), so this kernel keeps THREE key tiles in
 // flight per workgroup and halves the bytes:
 //   * a workgroup = 4 consecutive query views = 256 queries, as 4 waves x 64 queries (U = 2: a wave = one view = two 32-query MFMA tiles
@@ -22,8 +22,7 @@
 //
 // Three restructurings of the 4-wave form were built and measured in round 3 — an 8-wave workgroup of 64-query waves that reads every
 // K / V tile once (177 us), K / V resident in LDS with equal work per wave (188 us), the ring software-pipelined by one tile (273 us: 65
-// spilled registers) — all bit-identical to it and all slower than its 131 us at the bench shape; they live in
-// tools/variants/attention_dma_r3_records.hip, outside the product library.
+// spilled registers) — all bit-identical to it and all slower than its 131 us at the bench shape.
 //
 // FOLD (round 4).  The round-2 PMC pass (profiles/r2_new_kernels_pmc.txt) counts 17.6 vector instructions per MFMA — 560 per (64-query,
 // 64-key) unit of 32 MFMAs — so the per-score work was cut from {fma, exp2, add, 1/2 cvt, 1/2 max} to {exp2, add, 1/2 cvt, 1/2 max}:
@@ -64,24 +63,10 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 constexpr int DH = 64, KT = 64, QT = 256;
 constexpr int K_BYTES = KT * DH * 2;         // 8192
 constexpr int TILE_BYTES = 2 * K_BYTES;      // K image then V image
-#ifndef ADMA_RING
-#define ADMA_RING 4         // 4 slots = 64 KB: two workgroups per CU, three tiles in flight.  3 slots = 48 KB: THREE workgroups per CU, two tiles in flight, and the
-                            // first tile steps one ahead only (Q lands in slots 1-2, so tiles 1 and 2 are issued behind the first barrier) — build.py 'adma_ring3'
-#endif
-constexpr int RING = ADMA_RING;
-static_assert(RING == 3 || RING == 4, "ring depth");
+// 4 slots = 64 KB: two workgroups per CU, three tiles in flight (3 slots, three workgroups per CU and two tiles in flight, measured no faster: DESIGN.md)
+constexpr int RING = 4;
 constexpr float LOG2E = 1.4426950408889634f;
-#ifndef ADMA_PSWAP
-#define ADMA_PSWAP 1
-#endif
-#ifndef ADMA_HEAVY_FIRST
-#define ADMA_HEAVY_FIRST 1  // query blocks dispatched heaviest first (round 6); 0 = in index order (round 5)
-#endif
-#ifndef ADMA_REGROUP
-#define ADMA_REGROUP 1      // streams mask: query views grouped so that a workgroup's views share their key tiles (vf_common.h: vf_attn_query_groups); 0 = four
-                            // consecutive views per workgroup (build.py 'adma_consecutive')
-#endif
-// (round 5 A/B, removed with the view groups: ADMA_PAIRGRID — the query blocks of a (scene, head) adjacent on one XCD: fewer HBM re-reads, 20 % slower)
+// (round 5 A/B, removed with the view groups: the query blocks of a (scene, head) adjacent on one XCD: fewer HBM re-reads, 20 % slower)
 constexpr float ADMA_THR = 8.0f;             // a query's reference maximum moves when a tile exceeds it by more than this (exponent-of-2 units)
 
 __device__ __forceinline__ void bufds16(__amdgpu_buffer_rsrc_t r, void* l, unsigned voff, unsigned soff) {
@@ -112,27 +97,13 @@ __device__ __forceinline__ void wait_vm() {
 // v_permlane32_swap (one VALU instruction, gfx950) instead of ds_bpermute (an LDS round trip in the middle of the softmax's serial chain
 // plus six address instructions).  Both operands = x: r[0] = x of the low half-wave in all 64 lanes, r[1] = x of the high one
 __device__ __forceinline__ float xhalf_max(float x) {
-#if ADMA_PSWAP
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-#else
-    return fmaxf(x, __shfl_xor(x, 32, 64));
-#endif
 }
 __device__ __forceinline__ float xhalf_sum(float x) {
-#if ADMA_PSWAP
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);          // (low + high in every lane: the same sum the shuffle form makes in both half-waves)
-#else
-    return x + __shfl_xor(x, 32, 64);
-#endif
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);          // (low + high in every lane: the same sum in both half-waves)
 }
-
-#ifdef ADMA_STAMPS       // phase timeline (tools/microbench.py attn_stamps): per wave, cycles summed over its tile steps
-#define ADMA_STAMP(i) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt[i]) :: "memory")
-#else
-#define ADMA_STAMP(i)
-#endif
 
 // U = 32-query MFMA tiles per wave: 2 -> 4 waves of 64 queries, 1 -> 8 waves of 32 queries; both cover QT = 256 queries = 4 views
 template <bool DROP, int U>
@@ -222,11 +193,6 @@ __global__ __launch_bounds__(U == 2 ? 256 : 512, U == 2 ? 2 : 4) void attn_dma_k
         return t;
     };
 
-#ifdef ADMA_STAMPS
-    unsigned long long tt[8];
-    unsigned acc_t[6] = {0, 0, 0, 0, 0, 0};
-    ADMA_STAMP(7);
-#endif
     // ---- DMA.  Every 1 KB piece = 64 lanes x 16 B, lane-linear in LDS.
     // K piece (8 rows x 128 B): lane -> row (lane >> 3), LDS chunk c' = lane & 7 holds global chunk c' ^ ((row >> 1) & 7).
     // V piece (16 keys x 64 B of one feature half): lane -> key (lane >> 2), 16-byte chunk lane & 3.
@@ -256,8 +222,8 @@ __global__ __launch_bounds__(U == 2 ? 256 : 512, U == 2 ? 2 : 4) void attn_dma_k
         bufds16(q_rs, Qs + pi * 1024, (unsigned)(row * ldq * 2 + ((pc ^ ((r >> 1) & 7)) << 4)), 0u);
     }
     issue_tile(0);
-    if (RING == 4 && ntiles > 1) issue_tile(1);
-    if (RING == 4 && ntiles > 1) wait_vm<2 * LPT>(); else wait_vm<LPT>();         // Q has landed (vmcnt retires in issue order)
+    if (ntiles > 1) issue_tile(1);
+    if (ntiles > 1) wait_vm<2 * LPT>(); else wait_vm<LPT>();         // Q has landed (vmcnt retires in issue order)
     // Q fragments (B operand of S^T = K.Q^T): qb[u][ks] = Q[32 u + l31][16 ks + 8 half + 0..7] * scale * log2 e, re-rounded to bf16 (FOLD)
     const unsigned swz = (unsigned)((l31 >> 1) & 7);
     const float c2 = scale * LOG2E;
@@ -333,11 +299,7 @@ __global__ __launch_bounds__(U == 2 ? 256 : 512, U == 2 ? 2 : 4) void attn_dma_k
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float x = stu[t2][ks2 * 8 + e];
-#ifdef ADMA_X_NOSM
-            const float p = x;
-#else
             const float p = __builtin_amdgcn_exp2f(decltype(sub)::value ? x - dlt : x);
-#endif
             psum += p;                                               // the normaliser is over the undropped weights
             if constexpr (DROP) pk[e] = (__bf16)(vf_dropout_keep(w[e >> 2], e & 3, drop_thresh) ? p : 0.f);
             else pk[e] = (__bf16)p;
@@ -397,7 +359,6 @@ __global__ __launch_bounds__(U == 2 ? 256 : 512, U == 2 ? 2 : 4) void attn_dma_k
             }
         }
         seen = true;
-        ADMA_STAMP(4);
         // k-step (t2, ks2) = keys 32 t2 + 16 ks2 + 8 (e >> 2) + 4 half + (e & 3)
 #ifdef VF_X_TRINTRIN
 #pragma unroll
@@ -437,69 +398,32 @@ __global__ __launch_bounds__(U == 2 ? 256 : 512, U == 2 ? 2 : 4) void attn_dma_k
     // that one wave of a SIMD multiplies while the other exponentiates; ring two tiles ahead instead of three.  Bit-identical outputs,
     // 128 registers, and 2.3 % SLOWER in an in-process alternation (112.2 vs 109.7 us at the bench shape, 208 vs 204 us at S = 21):
     // profiles/r5_attention_ab.txt, commit "attention: skewed half-step schedule" in the history.)
-    ADMA_STAMP(6);
     for (int kt = 0; kt < ntiles; ++kt) {
         // this wave's pieces of tile kt have landed (counted: up to two later tiles stay in flight), its LDS reads of tile kt - 1 (and
         // of Q) are done; the barrier extends both to the workgroup, which frees the slot of tile kt - 1 (kt = 0: the Q slots)
-        ADMA_STAMP(0);
-        const int last_issued = RING == 4 ? min(ntiles - 1, kt == 0 ? 1 : kt + 2) : min(ntiles - 1, kt == 0 ? 0 : kt + 1);
+        const int last_issued = min(ntiles - 1, kt == 0 ? 1 : kt + 2);
         if (last_issued - kt >= 2) wait_vm_lgkm0<2 * LPT>();
         else if (last_issued - kt == 1) wait_vm_lgkm0<LPT>();
         else wait_vm_lgkm0<0>();
-        ADMA_STAMP(1);
         __builtin_amdgcn_s_barrier();
-        ADMA_STAMP(2);
-#ifdef ADMA_STAMPS
-        acc_t[0] += (unsigned)(tt[1] - tt[0]);                       // wait for the tile's DMA (and the wave's LDS reads)
-        acc_t[1] += (unsigned)(tt[2] - tt[1]);                       // wait at the barrier
-#endif
-#ifdef ADMA_X_NODMA
-        if (kt == 0) { issue_tile(ntiles > 2 ? 2 : 0); issue_tile(ntiles > 3 ? 3 : 0); }
-        else if (kt + 3 < ntiles) { asm volatile("s_nop 0"); }
-#else
         if (kt == 0) {
             if (ntiles > RING - 2) issue_tile(RING - 2);
             if (ntiles > RING - 1) issue_tile(RING - 1);
         } else if (kt + RING - 1 < ntiles) {
             issue_tile(kt + RING - 1);
         }
-#endif
-#ifdef ADMA_X_NOCOMPUTE
-        continue;
-#endif
         const int tcur = pop(rem_use, kt);                           // the key view in ring slot kt % RING
         // (a tile masked for all of the wave's queries contributes exactly 0.0f)
         const bool vis = dense ? (active && visible(qview, tcur)) : ((mine >> tcur) & 1ull) != 0ull;
         if (!vis) continue;
         f32x16 st[U][2];                                             // [query tile][key half]
-        ADMA_STAMP(3);
         scores(smem + (kt % RING) * TILE_BYTES, st);
         softmax_pv(st, smem + (kt % RING) * TILE_BYTES, tcur);
-#ifdef ADMA_STAMPS
-        ADMA_STAMP(5);
-        acc_t[2] += (unsigned)(tt[3] - tt[2]);                       // DMA issue + bookkeeping
-        acc_t[3] += (unsigned)(tt[4] - tt[3]);                       // S MFMAs issued + softmax done (the MFMAs' results consumed)
-        acc_t[4] += (unsigned)(tt[5] - tt[4]);                       // V^T reads + P.V MFMAs issued
-        acc_t[5] += 1u;                                              // visible tile steps of this wave
-#endif
     }
 
     // ---- normalise, round, transpose through the wave's slice of the (now idle) ring, store whole rows
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                                    // every wave is done with the ring
-#ifdef ADMA_STAMPS
-    {
-        unsigned long long te;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(te) :: "memory");
-        if (lse_out && lane == 0) {                                  // (the stamp build writes no log-sum-exp: the pointer carries the stamp buffer)
-            const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-            unsigned* o = reinterpret_cast<unsigned*>(lse_out) + (wg * NW + wave) * 8;
-            for (int i = 0; i < 6; ++i) o[i] = acc_t[i];
-            o[6] = (unsigned)(tt[6] - tt[7]);                        // kernel entry -> first tile step (Q in registers)
-            o[7] = (unsigned)(te - tt[6]);                           // the tile loop incl. the final barrier
-        }
-    }
-#endif
     if (!active) return;
     unsigned char* Os = smem + wave * QB;                            // [32 U queries][128 B], chunk c stored at c ^ ((row >> 1) & 7)
 #pragma unroll
@@ -507,10 +431,8 @@ __global__ __launch_bounds__(U == 2 ? 256 : 512, U == 2 ? 2 : 4) void attn_dma_k
         const float l_tot = xhalf_sum(l_run[u]);
         const float inv_l = (DROP ? drop_scale : 1.0f) / l_tot;
         const int row = u * 32 + l31;
-#ifndef ADMA_STAMPS
         // the training step's flash backward re-materialises P = exp(S scale - lse) from this per-query log-sum-exp (natural-log units)
         if (lse_out && half == 0) lse_out[((size_t)b * H + h) * T + qw0 + row] = __builtin_fmaf(m_ref[u], 0.69314718055994531f, logf(l_tot));      // (spelled as ONE fma: left to the compiler, the contraction depended on the code around it — 1-ulp differences between two builds of this file)
-#endif
 #pragma unroll
         for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -547,7 +469,7 @@ int vf_attn_dma_launch(const void* q, const void* k, const void* v, void* out, i
     if (drop_rate > 0.f && (unsigned long long)T * (unsigned long long)(T >> 2) >= (1ull << 32)) return VF_ERR_UNSUPPORTED;                   // 32-bit mask groups per plane
     const __bf16 *q_ = reinterpret_cast<const __bf16*>(q), *k_ = reinterpret_cast<const __bf16*>(k), *v_ = reinterpret_cast<const __bf16*>(v);
     __bf16* o_ = reinterpret_cast<__bf16*>(out);
-    const vf_attn_groups groups = vf_attn_query_groups(T / KT, twin_view, ADMA_REGROUP != 0, ADMA_HEAVY_FIRST != 0);
+    const vf_attn_groups groups = vf_attn_query_groups(T / KT, twin_view);
     const dim3 grid((unsigned)H, (unsigned)B, (unsigned)groups.n);
     const uint32_t thr = vf_dropout_thresh(drop_rate);
     const float dsc = 1.0f / (1.0f - drop_rate);

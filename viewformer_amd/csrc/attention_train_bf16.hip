@@ -6,12 +6,8 @@
 // LDS-DMA.  A streamed 64 x 64 tile is read in two ways — its rows as ds_read_b128 A fragments (k = features) and, through
 // ds_read_b64_tr_b16, its TRANSPOSE as A fragments (feature rows, k = the streamed rows) — and since the third session of round 6 ONE
 // 8 KB image per tile serves both (the "uni" image, dma_uni_piece below: a 4-row x 64-byte block per 256-byte bank line): 16-16.5 KB per
-// ring slot, three workgroups per CU.  The layouts it replaced (still here behind -DATB_KV_UNI=0 / -DATB_DQ_UNI=0 for A/B, same results
-// bit for bit) are attention_dma.hip's:
-//   * "rows" image of a 64 x 64 tile: 128-byte rows, 16-byte chunk index XORed with bits 1..3 of the row -> conflict-free ds_read_b128
-//     A fragments (rows of the streamed operand, k = features);
-//   * "tr" image: [feature half][row][32 features], read with ds_read_b64_tr_b16 -> the TRANSPOSED A fragment (feature rows, k = the
-//     streamed rows) straight from the row-major tile.
+// ring slot, three workgroups per CU.  It replaced attention_dma.hip's separate "rows" and "tr" images (two per operand, two workgroups per
+// CU), bit-identical and faster (dK / dV 98.0 -> 86.4 us with dropout: DESIGN.md).
 // Both kernels keep the owner's operands (dQ kernel: Q and dO rows of its 32 queries; dK/dV kernel: K and V rows of its 32 keys) in
 // registers as B fragments and compute the tile products with the owner in the MFMA column = lane, so P / dS sit in registers in the
 // B-operand layout of the accumulating MFMA (the k order of those products is the accumulator's row order, which is the order the
@@ -42,21 +38,6 @@ constexpr int DH = 64, KT = 64;
 constexpr int IMG = KT * DH * 2;             // one 64 x 64 bf16 image: 8 KB
 constexpr int OT = 128;                      // owner rows per workgroup: 4 waves x 32
 constexpr float LOG2E = 1.4426950408889634f;
-#ifndef ATB_ABL
-#define ATB_ABL 0           // ablation builds (results WRONG, timing only; build.py 'atb_abl*'): 1 = no "tr" image DMAs, 2 = no tile compute, 4 = no tile DMAs at all,
-                            // 9 = 1 + the tr reads aliased onto the rows images: slots of 2 images, ring 3, three workgroups per CU (the timing a unified image would have)
-#endif
-#ifndef ATB_KV_UNI
-#define ATB_KV_UNI 1        // dK / dV kernel: ONE LDS image per streamed operand serves the row reads AND the transposing reads (see dma_uni_piece); slots of two
-                            // images, ring of 3, three workgroups per CU.  0 = round 6's earlier form (rows image + tr image per operand, ring of 2; build.py 'dkv_two_images')
-#endif
-#ifndef ATB_DQ_UNI
-#define ATB_DQ_UNI 1        // dQ kernel: the K tile as ONE uni image (row reads for S^T, transposing reads for dQ^T), V as a uni image too; slots of two images
-                            // (48 KB ring: three workgroups per CU).  0 = K rows | V rows | K tr (build.py 'dq_three_images')
-#endif
-#ifndef ATB_HEAVY_FIRST
-#define ATB_HEAVY_FIRST 1   // owner blocks dispatched heaviest first (round 6, vf_common.h: vf_attn_block_order); 0 = in index order
-#endif
 // FOLD (round 6, dQ kernel; ADVICE r5 + VERDICT r5 item 2).  The forward kernel (attention_dma.hip) multiplies q by scale * log2 e and re-rounds
 // it to bf16 before its S product; until round 6 the backward re-materialised P from the UN-rounded q — an exponent off by |s| 2^-9, which
 // at the score magnitudes of a trained model (MIGT's scores are unscaled) is several per cent of P.  The dQ kernel holds q as its
@@ -77,28 +58,19 @@ __device__ __forceinline__ bf16x4 tr_read(const unsigned char* p) {
     const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(const_cast<unsigned char*>(p)));
     return __builtin_bit_cast(bf16x4, r);
 }
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p, int gap = 8 * 64) {             // 8 consecutive k of the accumulator order: two 4-row groups
-    const bf16x4 v0 = tr_read(p), v1 = tr_read(p + gap);
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p) {             // 8 consecutive k of the accumulator order: two 4-row groups, 1 KB apart
+    const bf16x4 v0 = tr_read(p), v1 = tr_read(p + 1024);
     bf16x8 a;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { a[e] = v0[e]; a[4 + e] = v1[e]; }
     return a;
 }
 
-struct Vis {
-    int Vc, Sv;
-    __device__ __forceinline__ bool operator()(int qv, int kv) const {
-        if (Sv > 0) {
-            const int qs = qv / Sv, qi = qv - qs * Sv;
-            const int ks = kv / Sv, ki = kv - ks * Sv;
-            return qs == 0 ? (ks == 0 && ki <= qi) : ((ks == 0 && ki < qi) || kv == qv);
-        }
-        return kv == qv || min(kv, Vc) < min(qv, Vc);
-    }
-};
+// the view mask: plain / twin (Vc = twin >= 0) / streams (Sv = -twin >= 2), as vf_attn_visible (vf_common.h)
+struct Vis { int Vc, Sv; };
 __device__ __forceinline__ Vis make_vis(int twin) { return Vis{twin >= 0 ? twin : 0x3fffffff, twin <= -2 ? -twin : 0}; }
-// the same relation as bit masks over views 0 .. nviews - 1 (nviews <= 64), in closed form: the kernels' prologues used to call visible() — two integer divisions
-// under the streams mask — for every (owner view, streamed view) pair and once more per tile step; ~120 divisions per workgroup before its first DMA could be issued
+// the relation as bit masks over views 0 .. nviews - 1 (nviews <= 64), in closed form: a loop over visible() costs two integer divisions under the
+// streams mask for every (owner view, streamed view) pair and once more per tile step; ~120 divisions per workgroup before its first DMA could be issued
 __device__ __forceinline__ unsigned long long vis_bits(int lo, int hi) {         // bits lo .. hi - 1
     if (hi <= lo || lo >= 64) return 0ull;
     const unsigned long long upto_hi = hi >= 64 ? ~0ull : ((1ull << hi) - 1ull);
@@ -132,36 +104,22 @@ __device__ __forceinline__ unsigned long long vis_queries_of(const Vis& V, int k
 
 template <int N>
 __device__ __forceinline__ void wait_loads() {                                   // this wave's loads: at most N outstanding; its LDS reads: done
+    static_assert(N == 0 || N == 4 || N == 6, "vmcnt immediates of these kernels");
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
     else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");
-}
-
-// a "rows" piece (8 rows x 128 B, lane -> row lane >> 3, LDS chunk lane & 7 = global chunk ^ ((row >> 1) & 7)) and a "tr" piece
-// (16 rows x 64 B of one feature half, lane -> row lane >> 2, chunk lane & 3) of a 64-row tile starting at row t * 64 of an operand
-// with row stride ld (elements)
-__device__ __forceinline__ void dma_rows_piece(__amdgpu_buffer_rsrc_t rs, unsigned char* img, int pi, int lane, int ld, int t) {
-    const int r = pi * 8 + (lane >> 3), pc = lane & 7;
-    bufds16(rs, img + pi * 1024, (unsigned)(r * ld * 2 + ((pc ^ ((r >> 1) & 7)) << 4)), (unsigned)(t * KT * ld * 2));
-}
-__device__ __forceinline__ void dma_tr_piece(__amdgpu_buffer_rsrc_t rs, unsigned char* img, int pi, int lane, int ld, int t) {
-    const int row = (pi & 3) * 16 + (lane >> 2);
-    bufds16(rs, img + pi * 1024, (unsigned)(row * ld * 2 + (pi >> 2) * 64 + (lane & 3) * 16), (unsigned)(t * KT * ld * 2));
+    else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
 }
 
 // "uni" image of a 64 x 64 bf16 tile (8 KB = 512 cells of 16 B; r = tile row, c = 16-byte chunk of its 128-byte row):
 //     cell(r, c) = 16 ((r >> 2) 2 + (c >> 2)) + 4 (r & 3) + ((c & 3) ^ m(r >> 2)),     m(j) = (j & 1) | ((j >> 2 & 1) << 1)
 // i.e. a block of 4 rows x 64 bytes is one 256-byte bank line, its 16 cells ordered [row & 3][chunk & 3 ^ m].
 //   * the transposing read of a 32x32x16 A fragment (ds_read_b64_tr_b16: per 32-lane pass 4 rows x 64 bytes of one feature half) takes exactly one
-//     bank line — conflict-free like the contiguous "tr" image;
+//     bank line — conflict-free;
 //   * the row read (ds_read_b128, lane = row, one chunk column per pass) is served in 16-lane passes over rows {0-3, 12-15, 20-27} / {4-11, 16-19,
 //     28-31}: r & 3 takes every value four times per pass, with r >> 2 in {0, 3, 5, 6} resp. {1, 2, 4, 7} — m() is distinct on each of the two sets, so
-//     the 16 rows land in 16 distinct 16-byte slots — conflict-free like the XOR-swizzled "rows" image.
-// The LDS side of the DMA is lane-linear (lane i of piece pi writes cell 64 pi + i), so the permutation sits on the SOURCE address
+//     the 16 rows land in 16 distinct 16-byte slots — conflict-free.
+// The LDS side of the DMA is lane-linear (lane i of piece pi writes cell 64 pi + i), so the permutation sits on the SOURCE address (the tile
+// starting at row t * 64 of an operand with row stride ld elements)
 __device__ __forceinline__ int uni_m(int j) { return (j & 1) | (((j >> 2) & 1) << 1); }
 __device__ __forceinline__ void dma_uni_piece(__amdgpu_buffer_rsrc_t rs, unsigned char* img, int pi, int lane, int ld, int t) {
     const int j = 2 * pi + (lane >> 5), d = (lane >> 4) & 1, slot = lane & 15;
@@ -246,14 +204,9 @@ __device__ __forceinline__ void store_transposed_bf16(const f32x16 (&acc)[2], un
 }
 
 // ---------------------------------------------------------------------------------------------------------------- dQ
-#ifndef ATB_DQ_RING
-#define ATB_DQ_RING 3              // 3 slots = 72 KB: two workgroups per CU, two tiles ahead.  2 slots (48 KB: three per CU, one tile ahead; build.py
-                                  // 'dq_ring2') measured the same within the order effect of an alternation (round 6: 162.3 vs 165.6 us for dQ + dK/dV
-                                  // as second library, 160.5 vs 160.3 as first; bit-identical): occupancy is not what holds this kernel back
-#endif
-constexpr bool DQ_UNI = ATB_DQ_UNI != 0 && !(ATB_ABL & 8);
-constexpr int DQ_TRK = (DQ_UNI || (ATB_ABL & 8)) ? 0 : 2 * IMG;
-constexpr int DQ_SLOT = DQ_TRK + IMG < 2 * IMG ? 2 * IMG : DQ_TRK + IMG, DQ_RING = ATB_DQ_RING, DQ_NL = (ATB_ABL & 4) ? 0 : (DQ_UNI || (ATB_ABL & 1)) ? 4 : 6;      // K rows | V rows | K tr; 6 one-KB pieces per wave and tile
+// a slot = K uni | V uni (16 KB); 4 one-KB pieces per wave and tile.  Ring of 3: two tiles ahead.  (A ring of 2 measured the same within the order
+// effect of an alternation in round 6, before the uni image — 162.3 vs 165.6 us for dQ + dK/dV as second library, 160.5 vs 160.3 as first)
+constexpr int DQ_SLOT = 2 * IMG, DQ_RING = 3, DQ_NL = 4;
 
 template <bool O16, bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
@@ -316,15 +269,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* 
 
     // key tiles some wave of this workgroup (two query views) sees
     const int va = q0 / KT, vb2 = va + 1;
-#ifdef VF_X_ATB_VISLOOP
-    unsigned long long need = 0;
-    for (int kt = 0; kt < nviews; ++kt)
-        if (visible(va, kt) || (vb2 < nviews && visible(vb2, kt))) need |= 1ull << kt;
-    const unsigned long long mine = 0ull;
-#else
     const unsigned long long need = vis_keys_of(visible, va, nviews) | (vb2 < nviews ? vis_keys_of(visible, vb2, nviews) : 0ull);
     const unsigned long long mine = active ? vis_keys_of(visible, qview, nviews) : 0ull;
-#endif
     const int n = __builtin_popcountll(need);
 
     auto issue = [&](int seq, int kt) {
@@ -332,15 +278,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* 
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int pi = wave * 2 + j;
-            if (ATB_ABL & 4) continue;
-            if constexpr (DQ_UNI) {
-                dma_uni_piece(k_rs, slot, pi, lane, ldk, kt);
-                dma_uni_piece(v_rs, slot + IMG, pi, lane, ldv, kt);
-                continue;
-            }
-            dma_rows_piece(k_rs, slot, pi, lane, ldk, kt);
-            dma_rows_piece(v_rs, slot + IMG, pi, lane, ldv, kt);
-            if (!(ATB_ABL & 1)) dma_tr_piece(k_rs, slot + DQ_TRK, pi, lane, ldk, kt);
+            dma_uni_piece(k_rs, slot, pi, lane, ldk, kt);
+            dma_uni_piece(v_rs, slot + IMG, pi, lane, ldv, kt);
         }
     };
     unsigned long long pend = need;                                  // tiles not issued yet
@@ -353,9 +292,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* 
     for (int d = 0; d < 2; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) ot[d][r] = 0.f;
-    const unsigned swz = (unsigned)((l31 >> 1) & 7);
-    const unsigned row_off = (unsigned)(l31 * 128);
-    const unsigned tr_off = (unsigned)((4 * half + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8);
     // uni image (dma_uni_piece): row-read base of row l31, transposing-read bases for the 8-row groups with (r >> 4) & 1 = ks2
     const int uni_ml = uni_m(l31 >> 2);
     const unsigned uni_row = (unsigned)(512 * (l31 >> 2) + 64 * (l31 & 3));
@@ -367,16 +303,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* 
     for (int i = 0; i < n; ++i) {
         const int kt = __builtin_ctzll(todo);
         todo &= todo - 1;
-        if (DQ_RING > 3 && issued - 2 > i) wait_loads<2 * DQ_NL>();               // tile i has landed (at most the next DQ_RING - 2 tiles are in flight)
-        else if (issued - 1 > i) wait_loads<DQ_NL>();
+        if (issued - 1 > i) wait_loads<DQ_NL>();                                  // tile i has landed (at most the next tile is in flight)
         else wait_loads<0>();
         __builtin_amdgcn_s_barrier();                                              // ... for every wave; the slot of tile i - 1 is free
         if (issued < n) { issue(issued, next_tile()); ++issued; }
-#ifdef VF_X_ATB_VISLOOP
-        if (!active || !visible(qview, kt) || (ATB_ABL & 2)) continue;
-#else
-        if (!((mine >> kt) & 1ull) || (ATB_ABL & 2)) continue;
-#endif
+        if (!((mine >> kt) & 1ull)) continue;
         const unsigned char* slot = smem + (i % DQ_RING) * DQ_SLOT;
 
         f32x16 st[2], dp[2];
@@ -389,8 +320,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* 
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
             for (int t2 = 0; t2 < 2; ++t2) {
-                const unsigned off = DQ_UNI ? uni_row + t2 * 4096 + (ks >> 1) * 256 + ((((unsigned)((ks & 1) * 2 + half)) ^ (unsigned)uni_ml) << 4)
-                                            : row_off + t2 * 4096 + ((((unsigned)(ks * 2 + half)) ^ swz) << 4);
+                const unsigned off = uni_row + t2 * 4096 + (ks >> 1) * 256 + ((((unsigned)((ks & 1) * 2 + half)) ^ (unsigned)uni_ml) << 4);
                 const bf16x8 a = *reinterpret_cast<const bf16x8*>(slot + off);
                 const bf16x8 c = *reinterpret_cast<const bf16x8*>(slot + IMG + off);
                 st[t2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qb[ks], st[t2], 0, 0, 0);      // S^T = K.Q^T
@@ -422,17 +352,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* 
 #ifdef VF_X_TRINTRIN
 #pragma unroll
                 for (int d = 0; d < 2; ++d) {
-                    const bf16x8 ka = DQ_UNI ? tr_frag(slot + DQ_TRK + uni_tr[ks2] + t2 * 4096 + ks2 * 2048 + d * 256, 1024)
-                                             : tr_frag(slot + DQ_TRK + tr_off + d * 4096 + (t2 * 32 + ks2 * 16) * 64);
+                    const bf16x8 ka = tr_frag(slot + uni_tr[ks2] + t2 * 4096 + ks2 * 2048 + d * 256);
                     ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, ds[t2][ks2], ot[d], 0, 0, 0);   // dQ^T += K^T.dS^T
                 }
 #else
             {   // (vf_tr_frag2_wait, vf_common.h: through the intrinsic these reads drained the DMA ring — the NEXT tile — before this product)
                 bf16x8 ka0, ka1;
-                if constexpr (DQ_UNI)
-                    vf_tr_frag2_wait(ka0, ka1, vf_lds_addr(slot) + uni_tr[ks2], DQ_TRK + t2 * 4096 + ks2 * 2048, DQ_TRK + t2 * 4096 + ks2 * 2048 + 256, 1024);
-                else
-                    vf_tr_frag2_wait(ka0, ka1, vf_lds_addr(slot) + tr_off, DQ_TRK + (t2 * 32 + ks2 * 16) * 64, DQ_TRK + 4096 + (t2 * 32 + ks2 * 16) * 64, 8 * 64);
+                vf_tr_frag2_wait(ka0, ka1, vf_lds_addr(slot) + uni_tr[ks2], t2 * 4096 + ks2 * 2048, t2 * 4096 + ks2 * 2048 + 256, 1024);
                 ot[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka0, ds[t2][ks2], ot[0], 0, 0, 0);      // dQ^T += K^T.dS^T
                 ot[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka1, ds[t2][ks2], ot[1], 0, 0, 0);
             }
@@ -446,10 +372,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const __bf16* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- dK, dV
-constexpr bool KV_UNI = ATB_KV_UNI != 0 && !(ATB_ABL & 8);
-constexpr int KV_QTR = (KV_UNI || (ATB_ABL & 8)) ? 0 : 2 * IMG, KV_DOTR = (KV_UNI || (ATB_ABL & 8)) ? IMG : 3 * IMG, KV_TAB = (KV_UNI || (ATB_ABL & 8)) ? 2 * IMG : 4 * IMG;
-constexpr int KV_NL = (ATB_ABL & 4) ? 2 : (KV_UNI || (ATB_ABL & 1)) ? 6 : 10;
-constexpr int KV_SLOT = KV_TAB + 512, KV_RING = (KV_UNI || (ATB_ABL & 8)) ? 3 : 2;      // Q rows | dO rows | Q tr | dO tr | lse[64] | D[64]; 10 loads per wave and tile
+constexpr int KV_DO = IMG, KV_TAB = 2 * IMG, KV_NL = 6;
+constexpr int KV_SLOT = KV_TAB + 512, KV_RING = 3;      // Q uni | dO uni | lse[64] | D[64]; 6 loads per wave and tile
 
 template <bool O16, bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
@@ -497,9 +421,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
     uint32_t drop_key = 0u, drop_k = 0u;
     const int drop_j = krow & 3;
     const float drop_cs = drop_scale * scale;
-#ifndef VF_X_DKV_ROT3
     const uint32_t drop_rr = vf_dropout_rotr(drop_j);
-#endif
     if constexpr (DROP) {
         drop_key = vf_dropout_key(drop_seed, drop_site, drop_plane0 + (uint32_t)(b * H + h));
         drop_k = (uint32_t)(krow >> 2) + (uint32_t)(4 * half) * (uint32_t)(T >> 2);
@@ -507,15 +429,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
 
     // query tiles that see a key view of this workgroup
     const int va = k0 / KT, vb2 = va + 1;
-#ifdef VF_X_ATB_VISLOOP
-    unsigned long long need = 0;
-    for (int qt = 0; qt < nviews; ++qt)
-        if (visible(qt, va) || (vb2 < nviews && visible(qt, vb2))) need |= 1ull << qt;
-    const unsigned long long mine = 0ull;
-#else
     const unsigned long long need = vis_queries_of(visible, va, nviews) | (vb2 < nviews ? vis_queries_of(visible, vb2, nviews) : 0ull);
     const unsigned long long mine = active ? vis_queries_of(visible, kview, nviews) : 0ull;
-#endif
     const int n = __builtin_popcountll(need);
 
     auto issue = [&](int seq, int qt) {
@@ -523,17 +438,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int pi = wave * 2 + j;
-            if (ATB_ABL & 4) continue;
-            if constexpr (KV_UNI) {
-                dma_uni_piece(q_rs, slot, pi, lane, ldq, qt);
-                dma_uni_piece(do_rs, slot + IMG, pi, lane, lddo, qt);
-                continue;
-            }
-            dma_rows_piece(q_rs, slot, pi, lane, ldq, qt);
-            dma_rows_piece(do_rs, slot + IMG, pi, lane, lddo, qt);
-            if (ATB_ABL & 1) continue;
-            dma_tr_piece(q_rs, slot + KV_QTR, pi, lane, ldq, qt);
-            dma_tr_piece(do_rs, slot + KV_DOTR, pi, lane, lddo, qt);
+            dma_uni_piece(q_rs, slot, pi, lane, ldq, qt);
+            dma_uni_piece(do_rs, slot + KV_DO, pi, lane, lddo, qt);
         }
         // lse / D of the tile's 64 queries (256 B each): 16 lanes x 16 B; every wave issues them (same bytes) so that all waves count
         // the same number of loads per tile
@@ -552,9 +458,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
     for (int d = 0; d < 2; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dvacc[d][r] = 0.f; dkacc[d][r] = 0.f; }
-    const unsigned swz = (unsigned)((l31 >> 1) & 7);
-    const unsigned row_off = (unsigned)(l31 * 128);
-    const unsigned tr_off = (unsigned)((4 * half + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8);
     // uni image (dma_uni_piece): this lane's row-read base (row l31 of a 32-row half, chunk column added per k-step) and its two transposing-read bases
     // (rows 4 half + ((lane & 15) >> 2) of an 8-row group whose (r >> 4) & 1 = ks2; 8-byte piece (lane & 3) of the 32-byte column block (lane >> 4) & 1)
     const int uni_ml = uni_m(l31 >> 2);
@@ -567,14 +470,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
     for (int i = 0; i < n; ++i) {
         const int qt = __builtin_ctzll(todo);
         todo &= todo - 1;
-        if (KV_RING > 2 && issued - 1 > i) wait_loads<KV_NL>(); else wait_loads<0>();   // (ring of 2: nothing else is in flight yet)
+        if (issued - 1 > i) wait_loads<KV_NL>(); else wait_loads<0>();
         __builtin_amdgcn_s_barrier();
         if (issued < n) { issue(issued, next_tile()); ++issued; }
-#ifdef VF_X_ATB_VISLOOP
-        if (!active || !visible(qt, kview) || (ATB_ABL & 2)) continue;
-#else
-        if (!((mine >> qt) & 1ull) || (ATB_ABL & 2)) continue;
-#endif
+        if (!((mine >> qt) & 1ull)) continue;
         const unsigned char* slot = smem + (i % KV_RING) * KV_SLOT;
 
 #pragma unroll
@@ -584,10 +483,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
             for (int r = 0; r < 16; ++r) { st[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const unsigned off = KV_UNI ? uni_row + u * 4096 + (ks >> 1) * 256 + ((((unsigned)((ks & 1) * 2 + half)) ^ (unsigned)uni_ml) << 4)
-                                            : row_off + u * 4096 + ((((unsigned)(ks * 2 + half)) ^ swz) << 4);
+                const unsigned off = uni_row + u * 4096 + (ks >> 1) * 256 + ((((unsigned)((ks & 1) * 2 + half)) ^ (unsigned)uni_ml) << 4);
                 const bf16x8 a = *reinterpret_cast<const bf16x8*>(slot + off);
-                const bf16x8 c = *reinterpret_cast<const bf16x8*>(slot + IMG + off);
+                const bf16x8 c = *reinterpret_cast<const bf16x8*>(slot + KV_DO + off);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kb[ks], st, 0, 0, 0);              // S = Q.K^T   [query][key]
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c, vb[ks], dp, 0, 0, 0);              // dP = dO.V^T
             }
@@ -612,34 +510,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
                 for (int e = 0; e < 4; ++e) {
                     const int r = 4 * j + e;
                     const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], c2, -l4[e] * LOG2E));
-                    float dpr = dp[r];
-                    bool keep = true;
-                    if constexpr (DROP) {
-#ifdef VF_X_DKV_HASH_PER_ELEMENT
-                        const uint32_t w = vf_dropout_word(drop_key, drop_k + (uint32_t)(qt * 64 + 32 * u + 8 * j + e) * (uint32_t)(T >> 2));
-#else
-                        const uint32_t w = w4[e];
-#endif
-#ifdef VF_X_DKV_ROT3
-                        keep = vf_dropout_keep(w, drop_j, drop_thresh);
-#else
-                        keep = vf_dropout_keep_rotr(w, drop_rr, drop_thresh);           // (one v_alignbit_b32 instead of shl / shr / or: same decision)
-#endif
-#ifdef VF_X_DKV_SEL2
-                        dpr = keep ? dpr * drop_scale : 0.f;
-#endif
-                    }
-#ifndef VF_X_DKV_SEL2
                     if constexpr (DROP) {
                         // one select instead of two: dS = scale (c keep P dP - P D) with keep P formed once (it is dV's operand too)
+                        const bool keep = vf_dropout_keep_rotr(w4[e], drop_rr, drop_thresh);     // (one v_alignbit_b32 instead of shl / shr / or: same decision)
                         const float pk = keep ? p : 0.f;
                         pf[r >> 3][r & 7] = (__bf16)pk;                         // (its 1 / (1 - rate) joins dV at the end)
-                        sf[r >> 3][r & 7] = (__bf16)__builtin_fmaf(pk, dpr * drop_cs, -(p * (d4[e] * scale)));
-                        continue;
+                        sf[r >> 3][r & 7] = (__bf16)__builtin_fmaf(pk, dp[r] * drop_cs, -(p * (d4[e] * scale)));
+                    } else {
+                        pf[r >> 3][r & 7] = (__bf16)p;
+                        sf[r >> 3][r & 7] = (__bf16)(p * (dp[r] - d4[e]) * scale);
                     }
-#endif
-                    pf[r >> 3][r & 7] = keep ? (__bf16)p : (__bf16)0.f;          // (its 1 / (1 - rate) joins dV at the end)
-                    sf[r >> 3][r & 7] = (__bf16)(p * (dpr - d4[e]) * scale);
                 }
             }
 #pragma unroll
@@ -647,17 +527,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(const __bf16*
 #pragma unroll
                 for (int d = 0; d < 2; ++d) {
 #ifdef VF_X_TRINTRIN
-                    const unsigned off = KV_UNI ? uni_tr[ks2] + u * 4096 + ks2 * 2048 + d * 256 : tr_off + d * 4096 + (u * 32 + ks2 * 16) * 64;
-                    const bf16x8 oa = tr_frag(slot + KV_DOTR + off, KV_UNI ? 1024 : 8 * 64);
-                    const bf16x8 qa = tr_frag(slot + KV_QTR + off, KV_UNI ? 1024 : 8 * 64);
+                    const unsigned off = uni_tr[ks2] + u * 4096 + ks2 * 2048 + d * 256;
+                    const bf16x8 oa = tr_frag(slot + KV_DO + off);
+                    const bf16x8 qa = tr_frag(slot + off);
 #else
                     bf16x8 oa, qa;      // (vf_tr_frag2_wait: as intrinsics these reads made hipcc wait for the NEXT tile's DMA — no overlap at all)
-                    if constexpr (KV_UNI)
-                        vf_tr_frag2_wait(oa, qa, vf_lds_addr(slot) + uni_tr[ks2], KV_DOTR + u * 4096 + ks2 * 2048 + d * 256,
-                                         KV_QTR + u * 4096 + ks2 * 2048 + d * 256, 1024);
-                    else
-                        vf_tr_frag2_wait(oa, qa, vf_lds_addr(slot) + tr_off, KV_DOTR + d * 4096 + (u * 32 + ks2 * 16) * 64,
-                                         KV_QTR + d * 4096 + (u * 32 + ks2 * 16) * 64, 8 * 64);
+                    vf_tr_frag2_wait(oa, qa, vf_lds_addr(slot) + uni_tr[ks2], KV_DO + u * 4096 + ks2 * 2048 + d * 256, u * 4096 + ks2 * 2048 + d * 256, 1024);
 #endif
                     dvacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, pf[ks2], dvacc[d], 0, 0, 0);   // dV^T += dO^T.P
                     dkacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, sf[ks2], dkacc[d], 0, 0, 0);   // dK^T += Q^T.dS
@@ -715,8 +590,8 @@ int vf_attn_bwd_bf16(const void* q, const void* k, const void* v, const void* do
     const int nblk = (T + OT - 1) / OT;
     if (nblk > 64) return VF_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)H, (unsigned)B, (unsigned)nblk);
-    const vf_attn_order ord_q = vf_attn_block_order(T / KT, OT / KT, nblk, twin_view, false, ATB_HEAVY_FIRST != 0);
-    const vf_attn_order ord_k = vf_attn_block_order(T / KT, OT / KT, nblk, twin_view, true, ATB_HEAVY_FIRST != 0);
+    const vf_attn_order ord_q = vf_attn_block_order(T / KT, OT / KT, nblk, twin_view, false);
+    const vf_attn_order ord_k = vf_attn_block_order(T / KT, OT / KT, nblk, twin_view, true);
     const __bf16 *q_ = reinterpret_cast<const __bf16*>(q), *k_ = reinterpret_cast<const __bf16*>(k), *v_ = reinterpret_cast<const __bf16*>(v),
                  *do_ = reinterpret_cast<const __bf16*>(dout);
     const uint32_t thr = vf_dropout_thresh(drop_rate);

@@ -19,13 +19,6 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VF_BF16_CONV_BUF
-#define VF_BF16_CONV_BUF 1
-#endif
-#ifndef VF_BF16_CONV_TALL
-#define VF_BF16_CONV_TALL 0     // A/B on MI355X: 694 vs 702 TF (128 ch @128^2), 994 vs 1004 (512 ch @16^2) — the weight stream is not this kernel's bound
-#endif
-
 constexpr int CK = 32;
 constexpr int P_LDB = 80;           // bytes per patch pixel in LDS
 constexpr int TH = 8, TW = 16;
@@ -125,23 +118,23 @@ __device__ __forceinline__ void halo_epilogue16(const vf_igemm_args& p, const f3
     }
 }
 
-// IO16: bit 0 = the input activation is bf16, bit 1 = the output (and the residual) are bf16
+// IO16: bit 1 = the output (and the residual) are bf16; bf16 input (bit 0) takes conv3_halo_bf16_w2_kernel below
 template <bool UP2, bool PRO, bool SWISH, bool PAIR = false, int IO16 = 0>
 __global__ __launch_bounds__(256, 2) void conv3_halo_bf16_kernel(vf_igemm_args p) {
     static_assert(!(PAIR && IO16), "the 8x8 pair tiles stay fp32");
-    constexpr bool IN16 = (IO16 & 1) != 0, OUT16 = (IO16 & 2) != 0;
+    static_assert(!(IO16 & 1), "bf16 input: conv3_halo_bf16_w2_kernel");
+    constexpr bool OUT16 = (IO16 & 2) != 0;
     using G = Geo<UP2, PAIR>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];   // [2][BUF]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // wave tile: TALL = all 128 pixels x 32 channels (4 x 1 MFMA tiles, half the weight bytes per wave) instead of 64 pixels x 64
-    // channels (2 x 2).  Unlike the x3h kernels it buys nothing here (see VF_BF16_CONV_TALL): at one MFMA per product the fp32
+    // wave tile: 64 pixels x 64 channels (2 x 2 MFMA tiles).  The x3h kernels' tall tile (all 128 pixels x 32 channels, half the weight bytes per
+    // wave) buys nothing here — A/B on MI355X: 694 vs 702 TF (128 ch @128^2), 994 vs 1004 (512 ch @16^2): at one MFMA per product the fp32
     // GroupNorm + swish prologue of the patch (two transcendentals per element) costs about as much as the MFMAs.
-    constexpr bool TALL = VF_BF16_CONV_TALL != 0;
-    constexpr int MI = TALL ? 4 : 2, NJ = TALL ? 1 : 2;
-    const int wave_m = TALL ? 0 : wave >> 1, wave_n = TALL ? wave : wave & 1;
+    constexpr int MI = 2, NJ = 2;
+    const int wave_m = wave >> 1, wave_n = wave & 1;
     const int half = lane >> 5, l31 = lane & 31;
 
     const int nb = p.Cout / BN;
@@ -158,8 +151,7 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_bf16_kernel(vf_igemm_args p
     const int sy0 = UP2 ? (y0 / 2 - 1) : (y0 - 1);
     const int sx0 = UP2 ? (x0 / 2 - 1) : (x0 - 1);
 
-    const float* __restrict__ X = IN16 ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(p.x) + (size_t)img * p.Hin * p.Win * p.Cin)
-                                       : p.x + (size_t)img * p.Hin * p.Win * p.Cin;
+    const float* __restrict__ X = p.x + (size_t)img * p.Hin * p.Win * p.Cin;
     const int nchunks = p.Cin / CK;
     const int last_stage = nchunks * 9 - 1;
 
@@ -185,30 +177,12 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_bf16_kernel(vf_igemm_args p
 
     f32x4 preg[G::SLOTS];
     f32x4 pa, pb, pa1, pb1;          // GroupNorm-apply folded to one fma: a = scale, b = beta - mean * scale (pa1 / pb1: the pair tile's 2nd image)
-#if VF_BF16_CONV_BUF      // buffer resources (SGPR base, scalar chunk / tap offset, 32-bit lane offsets) for the patch and the weight stream
+    // buffer resources (SGPR base, scalar chunk / tap offset, 32-bit lane offsets) for the patch and the weight stream
     const __amdgpu_buffer_rsrc_t x_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, 0x7fffffff, 0x00020000);
-#endif
     auto patch_load = [&](int chunk) {
-#if VF_BF16_CONV_BUF
 #pragma unroll
-        for (int q = 0; q < G::SLOTS; ++q) {
-            if constexpr (IN16) {                                   // four bf16 channels = 8 bytes per thread, widened exactly
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                const u32x2 w = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(x_rs, (unsigned)s_off[q] * 2u, (unsigned)(chunk * CK * 2), 0));
-                preg[q][0] = __builtin_bit_cast(float, w[0] << 16);
-                preg[q][1] = __builtin_bit_cast(float, w[0] & 0xffff0000u);
-                preg[q][2] = __builtin_bit_cast(float, w[1] << 16);
-                preg[q][3] = __builtin_bit_cast(float, w[1] & 0xffff0000u);
-            } else {
-                preg[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, (unsigned)s_off[q] * 4u, (unsigned)(chunk * CK * 4), 0));
-            }
-        }
-#else
-        static_assert(!IN16, "bf16 input needs the buffer-resource loads");
-        const float* xc = X + chunk * CK;
-#pragma unroll
-        for (int q = 0; q < G::SLOTS; ++q) preg[q] = *reinterpret_cast<const f32x4*>(xc + s_off[q]);
-#endif
+        for (int q = 0; q < G::SLOTS; ++q)
+            preg[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, (unsigned)s_off[q] * 4u, (unsigned)(chunk * CK * 4), 0));
         if (PRO) {
             const f32x4 pmean = *reinterpret_cast<const f32x4*>(p.pro_mean + (size_t)img * p.Cin + chunk * CK + c4 * 4);
             const f32x4 pbeta = *reinterpret_cast<const f32x4*>(p.pro_beta + chunk * CK + c4 * 4);
@@ -254,33 +228,19 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_bf16_kernel(vf_igemm_args p
     const int b_lane = (half * BN + wave_n * (32 * NJ) + l31) * 16;
     // software pipeline over taps (g = chunk*9 + tap): weight fragments BD taps ahead in a register ring, LDS fragments one
     // tap ahead; sched_barrier pins the distances (the scheduler otherwise sinks the loads next to their uses)
-#ifndef VF_BF16_BD
-#define VF_BF16_BD 2
-#endif
-    constexpr int BD = VF_BF16_BD, RING = BD + 1;
+    constexpr int BD = 2, RING = BD + 1;
     static_assert(9 % RING == 0, "ring indices must repeat per chunk");
     bf16x8 bring[RING][2 * NJ];
     bf16x8 aring[2][MI][2];
     const int last_g = nchunks * 9 - 1;
-#if VF_BF16_CONV_BUF
     const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(Wb), 0, 0x7fffffff, 0x00020000);
-#endif
     auto b_load = [&](bf16x8 (&dst)[2 * NJ], int g) {
-#if VF_BF16_CONV_BUF
         const unsigned soff = (unsigned)((size_t)min(g, last_g) * tap_stride);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 dst[ks * NJ + j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w_rs, (unsigned)((ks * 2 * BN + j * 32) * 16 + b_lane), soff, 0));
-#else
-        const unsigned char* src = Wb + (size_t)min(g, last_g) * tap_stride;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-                dst[ks * NJ + j] = *reinterpret_cast<const bf16x8*>(src + (ks * 2 * BN + j * 32) * 16 + b_lane);
-#endif
     };
     auto a_load = [&](bf16x8 (&dst)[MI][2], const unsigned char* patch, int tap) {
         const int dy = tap / 3, dx = tap % 3;
@@ -339,17 +299,7 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_bf16_kernel(vf_igemm_args p
 }
 
 
-#ifndef VF_BF16_CONV_W2
-#define VF_BF16_CONV_W2 1       // bf16-activation launches (IO16 == 3) on the two-wave kernel below (0: the four-wave kernel's IO16 = 3 form)
-#endif
-#ifndef VF_W2_ABL
-#define VF_W2_ABL 0             // ablation bits (WRONG results; tools/variants.sh builds only): 1 weight loads pinned to stage 0 (L1 hits), 2 LDS fragment
-#endif                          // reads once per chunk, 4 no epilogue stores, 8 no MFMAs, 16 no patch loads / stores after chunk 0
-#ifndef VF_BF16_W2_BD
-#define VF_BF16_W2_BD 2         // weight fragments this many (tap, k-step) stages ahead; ring of BD + 1 (must divide 18)
-#endif
-
-// The two-wave form for bf16 activations (round 4).  The four-wave kernel above gives a wave 64 pixels x 64 channels (2 x 2 MFMA tiles): per
+// The two-wave form for bf16 activations (round 4): every launch with bf16 input and output (IO16 = 3).  The four-wave kernel above gives a wave 64 pixels x 64 channels (2 x 2 MFMA tiles): per
 // 16-channel step 2 activation fragments (LDS) + 2 weight fragments (L2 -> L1 -> VGPR) feed 4 MFMAs, i.e. 0.5 KB through the vector-memory return
 // path per MFMA.  That path delivers 64 B / clk / CU and the CU's four matrix pipes retire one 32x32x16 MFMA per 8 clk: 0.5 KB / MFMA IS the return
 // path's peak, so the matrix pipe idled behind it (0.28 - 0.31 of the bf16 peak; the tall 4 x 1 tile moves the same problem to the LDS read path:
@@ -446,14 +396,14 @@ __global__ __launch_bounds__(128, 2) void conv3_halo_bf16_w2_kernel(vf_igemm_arg
     const unsigned char* __restrict__ Wb = reinterpret_cast<const unsigned char*>(p.w_packed) + (size_t)nblk * TAP_BYTES;
     const size_t tap_stride = (size_t)nb * TAP_BYTES;
     const int b_lane = (half * BN + wave_n * (32 * NJ) + l31) * 16;
-    constexpr int BD = VF_BF16_W2_BD, RB = BD + 1;
+    constexpr int BD = 2, RB = BD + 1;                     // weight fragments this many (tap, k-step) stages ahead
     static_assert(18 % RB == 0, "ring indices must repeat per chunk");
     bf16x8 bring[RB][NJ];
     bf16x8 aring[2][MI];
     const int last_g = nchunks * 9 - 1;
     const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(Wb), 0, 0x7fffffff, 0x00020000);
     auto b_load = [&](bf16x8 (&dst)[NJ], int g2) {
-        const unsigned soff = (VF_W2_ABL & 1) ? 0u : (unsigned)((size_t)min(g2 >> 1, last_g) * tap_stride);
+        const unsigned soff = (unsigned)((size_t)min(g2 >> 1, last_g) * tap_stride);
         const int ks = g2 & 1;
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
@@ -493,26 +443,21 @@ __global__ __launch_bounds__(128, 2) void conv3_halo_bf16_w2_kernel(vf_igemm_arg
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const unsigned char* patch = smem_h + (chunk & 1) * G::BUF;
         const bool more = chunk + 1 < nchunks;               // (the four-wave kernel re-stages the last chunk once more instead of branching)
-        if (!(VF_W2_ABL & 16) && more) patch_load(chunk + 1);
+        if (more) patch_load(chunk + 1);
         a_load(aring[0], patch, 0);
-        if (VF_W2_ABL & 2) a_load(aring[1], patch, 1);
 #pragma unroll
         for (int s = 0; s < 18; ++s) {
             b_load(bring[(s + BD) % RB], chunk * 18 + s + BD);
-            if (s + 1 < 18 && !(VF_W2_ABL & 2)) a_load(aring[(s + 1) & 1], patch, s + 1);
+            if (s + 1 < 18) a_load(aring[(s + 1) & 1], patch, s + 1);
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    if (VF_W2_ABL & 8) { acc[mi][j][0] += (float)aring[s & 1][mi][0] * (float)bring[s % RB][j][0]; }
-                    else acc[mi][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aring[s & 1][mi], bring[s % RB][j], acc[mi][j], 0, 0, 0);
-                }
+                for (int j = 0; j < NJ; ++j) acc[mi][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aring[s & 1][mi], bring[s % RB][j], acc[mi][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(VF_W2_ABL & 16) && (s & 1) && (s >> 1) < SLOTS && more) patch_store_slot((chunk + 1) & 1, s >> 1);
+            if ((s & 1) && (s >> 1) < SLOTS && more) patch_store_slot((chunk + 1) & 1, s >> 1);
         }
         __syncthreads();
     }
-    if ((VF_W2_ABL & 4) && acc[0][0][0] != 12345.678f) return;
     halo_epilogue16<MI, NJ>(p, acc, img, y0, x0, (ty * tilesX + tx) * 2, nblk, 0, wave_n, half, l31);
 }
 
@@ -567,14 +512,10 @@ int dispatch_io(const vf_igemm_args& a, hipStream_t s) {
     switch (a.reserved0 & 3) {                                      // bit 0: bf16 in; bit 1: bf16 out (+ bf16 residual)
         case 0: return dispatch_pro<UP2, false, 0>(a, s);
         case 2: return dispatch_pro<UP2, false, 2>(a, s);
-#if VF_BF16_CONV_W2
         case 3:
             if (a.Cin & 7) return VF_ERR_UNSUPPORTED;
             if (!a.pro_mean) return launch_halo_w2<UP2, false, false>(a, s);
             return a.pro_swish ? launch_halo_w2<UP2, true, true>(a, s) : launch_halo_w2<UP2, true, false>(a, s);
-#else
-        case 3: return dispatch_pro<UP2, false, 3>(a, s);
-#endif
         default: return VF_ERR_UNSUPPORTED;                        // (bf16 in, fp32 out: no caller)
     }
 }

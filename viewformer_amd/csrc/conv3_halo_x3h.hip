@@ -23,53 +23,13 @@
 #include <type_traits>
 #include "halo_common.h"
 
-#ifndef VF_X3H_BD
-#define VF_X3H_BD 2       // weight fragments are fetched this many stages ahead (register ring of BD + 1)
-#endif
-#ifndef VF_X3H_AD
-#define VF_X3H_AD 1       // LDS activation fragments are read this many stages ahead (0 or 1)
-#endif
-#ifndef VF_X3H_STORE
-#define VF_X3H_STORE 0
-#endif
-#ifndef VF_X3H_SB
-#define VF_X3H_SB 1       // sched_barrier(0) at every stage boundary (pins the prefetch distance)
-#endif
-#ifndef VF_X3H_S2_TALL
-#define VF_X3H_S2_TALL 1  // the stride-2 kernel's wave tile (see conv3_s2_x3h_kernel)
-#endif
-#ifndef VF_X3H_TALL
-#define VF_X3H_TALL 1     // wave tile = all 128 pixels x 32 channels (4 x 1 MFMA tiles) instead of 64 pixels x 64 channels (2 x 2): a stage
-#endif                    // then needs 2 weight fragments through the L1 -> VGPR return path instead of 4 (and 8 activation fragments
-                          // from LDS instead of 4).  PMC of the 2 x 2 form (profiles/r2_conv_x3h_l1path_pmc.txt): TD (the vector-memory
-                          // data-return unit) 92 % busy, TA 71 %, matrix pipe 54 % — the return path was the bound, LDS had 4x headroom.
-#ifndef VF_X3H_SKIP_LAST
-#define VF_X3H_SKIP_LAST 1  // the last chunk of a tile has no successor to stage: branch around the patch loads and the transform + split slots (the
-#endif                      // round-1..3 form re-staged the last chunk into the idle buffer: a fifth staging per four at 128 channels)
-#ifndef VF_X3H_PRECISE_SWISH
-#define VF_X3H_PRECISE_SWISH 0
-#endif
-
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VF_X3H_XBUF
-#define VF_X3H_XBUF 1       // patch loads of the stride-1 kernel through a per-image buffer resource
-#endif
-#ifndef VF_X3H_WFIRST
-#define VF_X3H_WFIRST 1
-#endif
-#ifndef VF_X3H_S2_WFIRST
-#define VF_X3H_S2_WFIRST 1
-#endif
-#ifndef VF_X3H_S2_WBUF
-#define VF_X3H_S2_WBUF 0    // the stride-2 kernel measured slower with buffer loads (240 vs 245 TF, 277 vs 296)
-#endif
-#ifndef VF_X3H_WBUF
-#define VF_X3H_WBUF 1       // weight fragments by buffer_load_dwordx4 (SGPR resource + scalar stage offset + 32-bit lane offset) instead of 64-bit lane addresses
-#endif
+// weight fragments of the stride-1 kernels by buffer_load_dwordx4 (SGPR resource + scalar stage offset + 32-bit lane offset) instead of 64-bit lane
+// addresses; the stride-2 kernel keeps plain loads (measured slower with buffer loads: 240 vs 245 TF, 277 vs 296)
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f16x8 wbuf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
@@ -106,9 +66,12 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_x3h_kernel(vf_igemm_args p)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr bool TALL = VF_X3H_TALL != 0;
-    constexpr int MI = TALL ? 4 : 2, NJ = TALL ? 1 : 2;           // MFMA tiles per wave: pixels (tile rows / 2) x channels / 32
-    const int wave_m = TALL ? 0 : wave >> 1, wave_n = TALL ? wave : wave & 1;
+    // wave tile = all 128 pixels x 32 channels (4 x 1 MFMA tiles) instead of 64 pixels x 64 channels (2 x 2): a stage then needs 2 weight fragments
+    // through the L1 -> VGPR return path instead of 4 (and 8 activation fragments from LDS instead of 4).  PMC of the 2 x 2 form
+    // (profiles/r2_conv_x3h_l1path_pmc.txt): TD (the vector-memory data-return unit) 92 % busy, TA 71 %, matrix pipe 54 % — the return path was the
+    // bound, LDS had 4x headroom.
+    constexpr int MI = 4, NJ = 1;                                  // MFMA tiles per wave: pixels (tile rows / 2) x channels / 32
+    const int wave_m = 0, wave_n = wave;
     const int half = lane >> 5, l31 = lane & 31;
 
     const int nb = p.Cout / BN;
@@ -154,20 +117,12 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_x3h_kernel(vf_igemm_args p)
 
     f32x4 preg[G::SLOTS];
     f32x4 pmean, pscale, pbeta, pmean1, pscale1;
-#if VF_X3H_XBUF
     // the image's activations as a buffer resource (an image is < 2 GB; the whole tensor is not): 32-bit lane offsets + a scalar chunk offset
     const __amdgpu_buffer_rsrc_t x_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, 0x7fffffff, 0x00020000);
-#endif
     auto patch_load = [&](int chunk) {
-#if VF_X3H_XBUF
 #pragma unroll
         for (int q = 0; q < G::SLOTS; ++q)
             preg[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, (unsigned)s_off[q] * 4u, (unsigned)(chunk * CK * 4), 0));
-#else
-        const float* xc = X + chunk * CK;
-#pragma unroll
-        for (int q = 0; q < G::SLOTS; ++q) preg[q] = *reinterpret_cast<const f32x4*>(xc + s_off[q]);
-#endif
         if (PRO) {
             pmean = *reinterpret_cast<const f32x4*>(p.pro_mean + (size_t)img * p.Cin + chunk * CK + c4 * 4);
             pscale = *reinterpret_cast<const f32x4*>(p.pro_scale + (size_t)img * p.Cin + chunk * CK + c4 * 4);
@@ -188,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_x3h_kernel(vf_igemm_args p)
                 const float mu = (PAIR && ((sel_mask >> q) & 1u)) ? pmean1[e] : pmean[e];
                 const float sc = (PAIR && ((sel_mask >> q) & 1u)) ? pscale1[e] : pscale[e];
                 t = (t - mu) * sc + pbeta[e];
-                if (SWISH) t = VF_X3H_PRECISE_SWISH ? vf_swish(t) : vf_swish_1ulp(t);
+                if (SWISH) t = vf_swish_1ulp(t);
             }
             _Float16 h, l;
             split2(((ok_mask >> q) & 1u) ? t : 0.f, h, l);
@@ -214,29 +169,19 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_x3h_kernel(vf_igemm_args p)
     const int b_lane = (half * BN + wave_n * (32 * NJ) + l31) * 16;
     // software pipeline over stages g = chunk*18 + tap*2 + ks: B two stages ahead in a 3-deep register ring (an L2 hit
     // costs about one stage of MFMA time, so one-ahead left the matrix pipe waiting), A one stage ahead (2-deep)
-    constexpr int BD = VF_X3H_BD, RING = BD + 1, AD = VF_X3H_AD;
-    static_assert(18 % RING == 0 && (AD == 0 || AD == 1), "ring indices must repeat per chunk");
+    constexpr int BD = 2, RING = BD + 1;
+    static_assert(18 % RING == 0, "ring indices must repeat per chunk");
     f16x8 bring[RING][2][NJ];
     f16x8 aring[2][MI][2];
     const int last_g = nchunks * 18 - 1;
-#if VF_X3H_WBUF
     const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(Wb), 0, 0x7fffffff, 0x00020000);
-#endif
     auto b_load = [&](f16x8 (&dst)[2][NJ], int g) {
         g = min(g, last_g);
-#if VF_X3H_WBUF
         const unsigned soff = (unsigned)((size_t)(g >> 1) * tap_stride + (g & 1) * KS_BYTES);
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) dst[pl][j] = wbuf_load(w_rs, (unsigned)(b_lane + pl * PLANE_BYTES + j * 32 * 16), soff);
-#else
-        const unsigned char* src = Wb + (size_t)(g >> 1) * tap_stride + (g & 1) * KS_BYTES + b_lane;
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) dst[pl][j] = *reinterpret_cast<const f16x8*>(src + pl * PLANE_BYTES + j * 32 * 16);
-#endif
     };
     auto a_load = [&](f16x8 (&dst)[MI][2], const unsigned char* patch, int s) {
         const int tap = s >> 1, ks = s & 1;
@@ -263,53 +208,31 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_x3h_kernel(vf_igemm_args p)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; accx[i][j][r] = 0.f; }
 
-#ifdef VF_X3H_STAMPS      // per-wave cycle sums (tools/microbench.py x3h_stamps): stage loop vs the wait at the chunk barrier; the tile's head and epilogue
-    unsigned long long st_t[3], st_k[4];
-    unsigned st_acc[2] = {0, 0};
-#define X3H_STAMP(i) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_t[i]) :: "memory")
-#define X3H_KSTAMP(i) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_k[i]) :: "memory")
-#else
-#define X3H_STAMP(i)
-#define X3H_KSTAMP(i)
-#endif
-    X3H_KSTAMP(0);
     patch_load(0);
 #pragma unroll
     for (int g = 0; g < BD; ++g) b_load(bring[g], g);
 #pragma unroll
     for (int q = 0; q < G::SLOTS; ++q) patch_store_slot(0, q);
     __syncthreads();
-    X3H_KSTAMP(1);
 
     for (int chunk = 0; chunk < nchunks; ++chunk) {
-        X3H_STAMP(0);
         const unsigned char* patch = smem_h + (chunk & 1) * G::BUF;
         // (vmcnt retires in issue order: stage BD's weight fragments go out BEFORE the patch loads, so that no fragment needed within the
         // next BD stages is queued behind HBM latency — see the stride-2 kernel, where this order is worth 20 %)
-#if VF_X3H_WFIRST
         b_load(bring[BD % RING], chunk * 18 + BD);
-#endif
-#ifdef VF_X3H_X_NOPATCH      // ablation: what do the next chunk's patch loads (HBM latency in front of the in-order vmcnt queue) cost?
-        if (chunk == 0)
-#endif
-        // A/B on one MI355X box, skip vs re-stage: 128 ch @128^2 365 vs 362 TF, @64^2 372 vs 365, stride 2 301 vs 295, 256 ch @32^2 equal; the
-        // 8x8 pair form LOSES 2 % (367 vs 374) and the upsampling form spills with the branch: both keep the old order
-        const bool more = !VF_X3H_SKIP_LAST || UP2 || PAIR || chunk + 1 < nchunks;
+        // the last chunk of a tile has no successor to stage: branch around the patch loads and the transform + split slots instead of re-staging
+        // it into the idle buffer.  A/B on one MI355X box, skip vs re-stage: 128 ch @128^2 365 vs 362 TF, @64^2 372 vs 365, stride 2 301 vs 295,
+        // 256 ch @32^2 equal; the 8x8 pair form LOSES 2 % (367 vs 374) and the upsampling form spills with the branch: both keep the old order
+        const bool more = UP2 || PAIR || chunk + 1 < nchunks;
         if (more) patch_load(min(chunk + 1, nchunks - 1));
-        if (AD) a_load(aring[0], patch, 0);
+        a_load(aring[0], patch, 0);                                  // LDS activation fragments one stage ahead
 #pragma unroll
         for (int s = 0; s < 18; ++s) {
-            if (!VF_X3H_WFIRST || s > 0) b_load(bring[(s + BD) % RING], chunk * 18 + s + BD);
-            if (AD == 0) a_load(aring[s & 1], patch, s);
-            else if (VF_X3H_SB != 3 && s + 1 < 18) a_load(aring[(s + 1) & 1], patch, s + 1);
-            if (VF_X3H_SB == 2) __builtin_amdgcn_sched_barrier(0);      // loads are issued before this stage's MFMAs
+            if (s > 0) b_load(bring[(s + BD) % RING], chunk * 18 + s + BD);
+            if (s + 1 < 18) a_load(aring[(s + 1) & 1], patch, s + 1);
             // three partial products (plane 0 = h, 1 = l * 2^11): the two cross terms into accx, the main term into acc
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                if (VF_X3H_SB == 3 && t == 1) {                         // LDS fragments of the next stage issued mid-stage
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (s + 1 < 18) a_load(aring[(s + 1) & 1], patch, s + 1);
-                }
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -320,20 +243,12 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_x3h_kernel(vf_igemm_args p)
                     }
             }
             // the next chunk's patch: one staging slot per odd stage (transform + split in the MFMA shadow)
-            if (VF_X3H_SB == 1 || VF_X3H_SB == 3) __builtin_amdgcn_sched_barrier(0);
-            if ((s & 1) && (s >> 1) >= VF_X3H_STORE && (s >> 1) - VF_X3H_STORE < G::SLOTS && more) patch_store_slot((chunk + 1) & 1, (s >> 1) - VF_X3H_STORE);
-            if (VF_X3H_SB == 2) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);                           // at every stage boundary: pins the prefetch distance
+            if ((s & 1) && (s >> 1) < G::SLOTS && more) patch_store_slot((chunk + 1) & 1, s >> 1);
         }
-        X3H_STAMP(1);
         __syncthreads();
-#ifdef VF_X3H_STAMPS
-        X3H_STAMP(2);
-        st_acc[0] += (unsigned)(st_t[1] - st_t[0]);
-        st_acc[1] += (unsigned)(st_t[2] - st_t[1]);
-#endif
     }
 
-    X3H_KSTAMP(2);
     // out = (acc + accx * 2^-11) / S with S the power-of-two weight scale stored behind the packed planes
     const float inv_s = *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(p.w_packed) + (size_t)nchunks * 9 * nb * TAP_BYTES);
 #pragma unroll
@@ -343,17 +258,6 @@ __global__ __launch_bounds__(256, 2) void conv3_halo_x3h_kernel(vf_igemm_args p)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = __builtin_fmaf(accx[i][j][r], 4.8828125e-4f, acc[i][j][r]) * inv_s;
     vf_halo_epilogue_t<PAIR, MI, NJ>(p, acc, img, img1, y0, x0, PAIR ? 0 : (ty * tilesX + tx) * 2, nblk, wave_m, wave_n, half, l31);
-#ifdef VF_X3H_STAMPS      // behind the GroupNorm partials of the launch (the caller sizes gn_part for it)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (the epilogue's stores have been accepted)
-    X3H_KSTAMP(3);
-    if (p.gn_part && lane == 0) {
-        unsigned* o = reinterpret_cast<unsigned*>(p.gn_part + (size_t)n_img_total * p.gn_slots * 64) + ((size_t)blockIdx.x * 4 + wave) * 4;
-        o[0] = st_acc[0];
-        o[1] = st_acc[1];
-        o[2] = (unsigned)(st_k[1] - st_k[0]);
-        o[3] = (unsigned)(st_k[3] - st_k[2]);
-    }
-#endif
 }
 
 
@@ -384,12 +288,11 @@ __global__ __launch_bounds__(256, 2) void conv3_s2_x3h_kernel(vf_igemm_args p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // wave tile: S2 TALL = all 128 output pixels x 32 channels (4 x 1 MFMA tiles): every weight fragment streamed L2 -> VGPR feeds 4
+    // wave tile: all 128 output pixels x 32 channels (4 x 1 MFMA tiles): every weight fragment streamed L2 -> VGPR feeds 4
     // pixel tiles and no two waves load the same fragment — the 2 x 2 form moved 147 KB of weights + 36 KB of patch per 16-channel
     // chunk through the CU's L1 path for 14 MFLOP (77 FLOP/B: a 30 % matrix-pipe ceiling at ~16 B/clk/CU; it measured 28 %)
-    constexpr bool TALL = VF_X3H_S2_TALL != 0;
-    constexpr int MI = TALL ? 4 : 2, NJ = TALL ? 1 : 2;
-    const int wave_m = TALL ? 0 : wave >> 1, wave_n = TALL ? wave : wave & 1;
+    constexpr int MI = 4, NJ = 1;
+    const int wave_m = 0, wave_n = wave;
     const int half = lane >> 5, l31 = lane & 31;
 
     const int nb = p.Cout / BN;
@@ -470,25 +373,14 @@ __global__ __launch_bounds__(256, 2) void conv3_s2_x3h_kernel(vf_igemm_args p) {
     constexpr int S2_BR = 3;                         // weight-fragment ring depth: must divide the 9 taps (the slot is indexed by the tap)
     f16x8 bring[S2_BR][2][NJ];
     f16x8 aring[2][MI][2];
-#if VF_X3H_S2_WBUF
-    const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(Wb), 0, 0x7fffffff, 0x00020000);
-#endif
     auto b_load = [&](f16x8 (&dst)[2][NJ], int g) {            // g = chunk16 * 9 + tap
         g = min(g, last_g);
         const int c = g / 9, tap = g - c * 9;
-#if VF_X3H_S2_WBUF
-        const unsigned soff = (unsigned)((size_t)((c >> 1) * 9 + tap) * tap_stride + (c & 1) * KS_BYTES);
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) dst[pl][j] = wbuf_load(w_rs, (unsigned)(b_lane + pl * PLANE_BYTES + j * 32 * 16), soff);
-#else
         const unsigned char* src = Wb + (size_t)((c >> 1) * 9 + tap) * tap_stride + (c & 1) * KS_BYTES + b_lane;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) dst[pl][j] = *reinterpret_cast<const f16x8*>(src + pl * PLANE_BYTES + j * 32 * 16);
-#endif
     };
     auto a_load = [&](f16x8 (&dst)[MI][2], int tap) {
         const int dy = tap / 3, dx = tap % 3;
@@ -516,18 +408,13 @@ __global__ __launch_bounds__(256, 2) void conv3_s2_x3h_kernel(vf_igemm_args p) {
         // vmcnt retires loads in issue order: a weight fragment issued AFTER the next chunk's patch loads (HBM latency) cannot be consumed
         // before they have landed.  So tap 2's fragments go out first — the patch then has until tap 3 instead of tap 2 (without the
         // patch loads at all the kernel runs 354 instead of 240 TF: that wait is its bound).
-#if VF_X3H_S2_WFIRST
         b_load(bring[(S2_BR - 1) % S2_BR], chunk * 9 + S2_BR - 1);
-#endif
-#ifdef VF_X3H_X_NOPATCH
-        if (chunk == 0)
-#endif
-        if (!VF_X3H_SKIP_LAST || chunk + 1 < nchunks) patch_load(min(chunk + 1, nchunks - 1));
+        if (chunk + 1 < nchunks) patch_load(min(chunk + 1, nchunks - 1));
         __syncthreads();
         a_load(aring[0], 0);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            if (!VF_X3H_S2_WFIRST || t > 0) b_load(bring[(t + S2_BR - 1) % S2_BR], chunk * 9 + t + S2_BR - 1);
+            if (t > 0) b_load(bring[(t + S2_BR - 1) % S2_BR], chunk * 9 + t + S2_BR - 1);
             if (t + 1 < 9) a_load(aring[(t + 1) & 1], t + 1);
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
@@ -570,19 +457,9 @@ __global__ __launch_bounds__(256, 2) void conv3_s2_x3h_kernel(vf_igemm_args p) {
 // the results differ in the last bits: both are fp32-equivalent to the same bound (tests/test_hip_x3h.py) and both reproduce every one of the
 // 20 480 reference-recorded tokens (tests/test_hip_parity_scale.py).  Stride 1, no pair tiles, an even number of 32-channel chunks.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-#ifndef X3H16_LB
-#define X3H16_LB 2
-#endif
-#ifndef X3H16_PKXFORM
-#define X3H16_PKXFORM 0         // 1 = the staging transform on packed fp32 instructions (build.py variant 'x3h16_pk_xform'): same bits, a third fewer vector
-                                // instructions per staged value — and 2.5-4 % SLOWER (profiles/r6_conv_ab.txt): measured in round 6, not shipped
-#endif
-#ifndef VF_X3H16_ABL
-#define VF_X3H16_ABL 0          // ablation bits (WRONG results; tools/variants.sh builds only): 1 weight fragments pinned to tap 0, 2 patch fragments read once per
-#endif                          // chunk, 4 no epilogue, 8 no MFMAs, 16 no next-chunk staging (DMA + transform), 32 staging without the transform
 
 template <bool PRO, bool SWISH>
-__global__ __launch_bounds__(256, X3H16_LB) void conv3_halo_x3h16_kernel(vf_igemm_args p) {
+__global__ __launch_bounds__(256, 2) void conv3_halo_x3h16_kernel(vf_igemm_args p) {
     using G = Geo<false, false>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];   // [2][BUF]
     constexpr int RT = 8, CT = 2;                      // accumulator tiles per wave: tile rows x 16-channel tiles
@@ -676,38 +553,19 @@ __global__ __launch_bounds__(256, X3H16_LB) void conv3_halo_x3h16_kernel(vf_igem
         f32x4 raw = {0.f, 0.f, 0.f, 0.f};                        // (slot 5 of wave 3 has no landing area: pixels 184 .. 191 do not exist)
         if (!(q == G::SLOTS - 1 && wave == 3)) raw = *reinterpret_cast<const f32x4*>(raw_l + q * 4096 + tid * 16);
         f16x4 oh, ol;
-#if X3H16_PKXFORM && !VF_X3H_PRECISE_SWISH
-        // the GroupNorm-apply + swish + split of two values at a time on packed fp32 instructions (vf_common.h: vf_swish_1ulp_pk): the same
-        // operations in the same order as the scalar form below — same bits, a third fewer vector instructions per staged value (A/B only: slower)
-        const bool okq = ((ok_mask >> q) & 1u) != 0u;
-#pragma unroll
-        for (int e2 = 0; e2 < 2; ++e2) {
-            vf_f32x2 t = {raw[2 * e2], raw[2 * e2 + 1]};
-            if (PRO && !(VF_X3H16_ABL & 32)) {
-                const vf_f32x2 m2 = {pmean[2 * e2], pmean[2 * e2 + 1]}, s2 = {pscale[2 * e2], pscale[2 * e2 + 1]}, b2 = {pbeta[2 * e2], pbeta[2 * e2 + 1]};
-                t = (t - m2) * s2 + b2;
-                if (SWISH) t = vf_swish_1ulp_pk(t);
-            }
-            if (!okq) t = (vf_f32x2){0.f, 0.f};
-            const _Float16 h0 = (_Float16)t.x, h1 = (_Float16)t.y;
-            const vf_f32x2 hb = {(float)h0, (float)h1}, k2048 = {2048.f, 2048.f};
-            const vf_f32x2 lo = (t - hb) * k2048;
-            oh[2 * e2] = h0; oh[2 * e2 + 1] = h1;
-            ol[2 * e2] = (_Float16)lo.x; ol[2 * e2 + 1] = (_Float16)lo.y;
-        }
-#else
+        // (the same transform on packed fp32 instructions — same bits, a third fewer vector instructions per staged value — measured 2.5-4 % SLOWER:
+        // profiles/r6_conv_ab.txt)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float t = raw[e];
-            if (PRO && !(VF_X3H16_ABL & 32)) {
+            if (PRO) {
                 t = (t - pmean[e]) * pscale[e] + pbeta[e];
-                if (SWISH) t = VF_X3H_PRECISE_SWISH ? vf_swish(t) : vf_swish_1ulp(t);
+                if (SWISH) t = vf_swish_1ulp(t);
             }
             _Float16 h, l;
             split2(((ok_mask >> q) & 1u) ? t : 0.f, h, l);
             oh[e] = h; ol[e] = l;
         }
-#endif
         *reinterpret_cast<f16x4*>(dst) = oh;
         *reinterpret_cast<f16x4*>(dst + 64) = ol;
     };
@@ -721,13 +579,10 @@ __global__ __launch_bounds__(256, X3H16_LB) void conv3_halo_x3h16_kernel(vf_igem
     const int last_tap = nchunks * 9 - 1;
     const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(Wb), 0, 0x7fffffff, 0x00020000);
     f16x8 bring[2][4];                                              // [tap parity][h ct0, h ct1, l' ct0, l' ct1]
-#ifndef X3H16_AR
-#define X3H16_AR 3
-#endif
-    constexpr int AR = X3H16_AR;                                    // patch-fragment ring: AR - 1 tile rows ahead (AR divides 72)
+    constexpr int AR = 3;                                           // patch-fragment ring: AR - 1 tile rows ahead (AR divides 72)
     f16x8 aring[AR][2];                                             // [tile-row step % AR][h, l']
     auto b_load = [&](f16x8 (&dst)[4], int gtap) {
-        const unsigned soff = (VF_X3H16_ABL & 1) ? 0u : (unsigned)((size_t)min(gtap, last_tap) * tap_stride);
+        const unsigned soff = (unsigned)((size_t)min(gtap, last_tap) * tap_stride);
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
@@ -763,7 +618,7 @@ __global__ __launch_bounds__(256, X3H16_LB) void conv3_halo_x3h16_kernel(vf_igem
     auto chunk_body = [&](int chunk, auto parity) {
         constexpr int P0 = decltype(parity)::value;
         const unsigned char* patch = smem_h + P0 * G::BUF;
-        const bool more = chunk + 1 < nchunks && !(VF_X3H16_ABL & 16);
+        const bool more = chunk + 1 < nchunks;
         // (vmcnt retires in issue order: the next tap's weights go out BEFORE the patch loads)
         b_load(bring[(P0 + 1) & 1], chunk * 9 + 1);
         // The DMAs sit behind `if (more)`; where that branch rejoins, hipcc's s_waitcnt pass takes the STRICTER path's pending count — the one
@@ -788,20 +643,14 @@ __global__ __launch_bounds__(256, X3H16_LB) void conv3_halo_x3h16_kernel(vf_igem
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 const int step = t * 8 + rt;
-                if (step + AR - 1 < 72 && !((VF_X3H16_ABL & 2) && step + AR - 1 >= AR)) a_load(aring[(step + AR - 1) % AR], patch, step + AR - 1);
+                if (step + AR - 1 < 72) a_load(aring[(step + AR - 1) % AR], patch, step + AR - 1);
                 const f16x8 ah = aring[step % AR][0], al = aring[step % AR][1];
-#if VF_X3H16_ABL & 8
-                accx[rt][0][0] += (float)al[0] * (float)B[0][0]; accx[rt][1][0] += (float)al[1] * (float)B[1][0];
-                acc[rt][0][0] += (float)ah[0] * (float)B[0][1]; acc[rt][1][0] += (float)ah[1] * (float)B[1][1];
-                accx[rt][0][1] += (float)ah[2] * (float)B[2][0]; accx[rt][1][1] += (float)ah[3] * (float)B[3][0];
-#else
                 accx[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, B[0], accx[rt][0], 0, 0, 0);
                 accx[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, B[1], accx[rt][1], 0, 0, 0);
                 acc[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, B[0], acc[rt][0], 0, 0, 0);
                 acc[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, B[1], acc[rt][1], 0, 0, 0);
                 accx[rt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, B[2], accx[rt][0], 0, 0, 0);
                 accx[rt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, B[3], accx[rt][1], 0, 0, 0);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (t >= 1 && t <= G::SLOTS && more) {                                            // the next chunk's patch, one slot per tap
@@ -818,7 +667,6 @@ __global__ __launch_bounds__(256, X3H16_LB) void conv3_halo_x3h16_kernel(vf_igem
         chunk_body(chunk + 1, std::integral_constant<int, 1>{});
     }
 
-    if ((VF_X3H16_ABL & 4) && acc[0][0][0] + accx[7][1][3] != 12345.678f) return;
     // ---- epilogue: out = (acc + accx * 2^-11) / S + bias (+ residual); GroupNorm partials of the stored values (fp64 sums, rounded once)
     const float inv_s = *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(p.w_packed) + (size_t)nchunks * 9 * nb * TAP_BYTES);
     // (buffer resources per image + a lane offset + a scalar (tile row, pixel) offset: 64-bit lane addresses for the 32 pixels of a lane cost 64
@@ -930,16 +778,10 @@ __global__ void pack_conv_x3h_kernel(const float* __restrict__ w, _Float16* __re
 template <bool UP2, bool PRO, bool SWISH, bool PAIR>
 int launch_halo(const vf_igemm_args& a, hipStream_t stream) {
     using G = Geo<UP2, PAIR>;
-#ifndef VF_X3H_LDS_PAD
-#define VF_X3H_LDS_PAD 0    // probe: extra LDS bytes per workgroup (> 28 KB: one workgroup per CU, i.e. one wave per SIMD — profiles/r4_power_ceiling_probe.txt)
-#endif
-    const size_t smem = (size_t)2 * G::BUF + VF_X3H_LDS_PAD;
+    const size_t smem = (size_t)2 * G::BUF;
     const int n_img = a.M / (a.Hout * a.Wout);
     const long long blocks = PAIR ? (long long)((n_img + 1) / 2) * (a.Cout / BN)
                                   : (long long)n_img * (a.Hout / TH) * (a.Wout / TW) * (a.Cout / BN);
-#if VF_X3H_LDS_PAD
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_halo_x3h_kernel<UP2, PRO, SWISH, PAIR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
     hipLaunchKernelGGL((conv3_halo_x3h_kernel<UP2, PRO, SWISH, PAIR>), dim3((unsigned)blocks), dim3(256), smem, stream, a);
     return vf_last_status();
 }

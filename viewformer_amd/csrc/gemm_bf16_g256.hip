@@ -26,9 +26,6 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
-#ifndef G256_PANEL
-#define G256_PANEL 4          // column tiles per panel (0: all column tiles of a row block together)
-#endif
 // (Measured and removed, in the history with their numbers: the A tile through VGPRs (round 2), a persistent one-workgroup-per-CU form that
 // issues the next tile's first stage before its epilogue — a wash, round 3 —, row groups inside an XCD — more FETCH, 4-5 % slower, round 5,
 // profiles/r5_gemm_g256_tile_order.txt —, a 16x16x32-MFMA feasibility probe.)
@@ -290,32 +287,15 @@ __device__ __forceinline__ void g256_tile(const vf_igemm_args& p, unsigned char*
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-#ifdef G256_STAMPS       // phase timeline (tools/microbench.py g256_stamps): per wave, cycles summed over the stages
-    unsigned long long tt[6];
-    unsigned acc_t[6] = {0, 0, 0, 0, 0, 0};
-#define G256_STAMP(i) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt[i]) :: "memory")
-    G256_STAMP(5);
-#else
-#define G256_STAMP(i)
-#endif
     // (A first-round stagger — four groups of CUs 4 000-16 000 cycles apart, so that the 256 epilogues of a round do not reach the memory system
     // together — was measured in round 3 and removed: 388 -> 397-400 us for c_fc at M = 65 536, the tail it adds outweighs what it spreads.)
     issue(0);
     for (int s = 0; s < nstages; ++s) {
         // stage s has landed (this wave's pieces: vmcnt; everyone's: the barrier); every wave has finished reading stage s - 1
         // (lgkmcnt: the compiler may leave the last ds_reads in flight up to their MFMA), whose buffer the next DMA overwrites
-        G256_STAMP(3);                                     // MFMAs issued (fragments all consumed)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        G256_STAMP(4);                                     // own DMA pieces landed
         __builtin_amdgcn_s_barrier();
-        G256_STAMP(0);                                     // barrier passed
-#ifdef G256_STAMPS
-        acc_t[3] += (unsigned)(tt[4] - tt[3]);             // wait for the DMA
-        acc_t[4] += (unsigned)(tt[0] - tt[4]);             // wait at the barrier
-        if (s > 0) acc_t[2] += (unsigned)(tt[3] - tt[2]);  // MFMA phase of the previous stage
-#endif
         if (s + 1 < nstages) issue(s + 1);
-        G256_STAMP(1);                                     // DMA issued
         const unsigned char* buf = smem_b + (s & 1) * GSTAGE;
         // fragments of k-step ks + 1 are read while the 2 IC MFMAs of k-step ks run (two register sets)
         bf16x8 a[2][IC], b[2][2];
@@ -326,12 +306,6 @@ __device__ __forceinline__ void g256_tile(const vf_igemm_args& p, unsigned char*
             for (int i = 0; i < IC; ++i) af[i] = *reinterpret_cast<const bf16x8*>(buf + a_off[ks] + i * (32 * 128));
         };
         frags(0, a[0], b[0]);
-#ifdef G256_STAMPS
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        G256_STAMP(2);                                     // first fragments in registers
-        acc_t[0] += (unsigned)(tt[1] - tt[0]);
-        acc_t[1] += (unsigned)(tt[2] - tt[1]);
-#endif
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             if (ks < 3) frags(ks + 1, a[(ks + 1) & 1], b[(ks + 1) & 1]);
@@ -345,15 +319,6 @@ __device__ __forceinline__ void g256_tile(const vf_igemm_args& p, unsigned char*
         }
     }
 
-#ifdef G256_STAMPS
-    G256_STAMP(3);
-    acc_t[2] += (unsigned)(tt[3] - tt[2]);
-    if (p.pro_beta && lane == 0) {                         // (the GEMM has no prologue: the pointer carries the stamp buffer)
-        unsigned* o = reinterpret_cast<unsigned*>(const_cast<float*>(p.pro_beta)) + ((size_t)blockIdx.x * 8 + wave) * 8;
-        for (int i = 0; i < 5; ++i) o[i] = acc_t[i];
-        o[5] = (unsigned)(tt[3] - tt[5]);                  // kernel entry -> end of the main loop
-    }
-#endif
     const bool full = m_tile0 + TROWS <= p.M;
     const bool gelu = p.epilogue == VF_EPI_GELU_ERF;
     if (O16) {
@@ -381,27 +346,14 @@ __device__ __forceinline__ void g256_tile(const vf_igemm_args& p, unsigned char*
     } else {
         g256_store_f32<DROP, IC>(p, acc, m_tile0, n_tile0, wrow0, wave_n, half, l31, full, gelu);
     }
-#ifdef G256_STAMPS
-    {   // epilogue: [6] = bias / convert / store instructions issued, [7] = the stores drained (vmcnt 0)
-        unsigned long long te0, te1;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(te0) :: "memory");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(te1) :: "memory");
-        if (p.pro_beta && lane == 0) {
-            unsigned* o = reinterpret_cast<unsigned*>(const_cast<float*>(p.pro_beta)) + ((size_t)blockIdx.x * 8 + wave) * 8;
-            o[6] = (unsigned)(te0 - tt[3]);
-            o[7] = (unsigned)(te1 - te0);
-        }
-    }
-#endif
 }
 
 // column panels of sn column tiles over mt row tiles (the round-2 order): logical id -> (row tile, column tile).  The ~32 workgroups an XCD
 // runs at a time are then ~8 row blocks x sn column tiles, whose weight panel (sn x 393 KB at K = 768) stays in the XCD's 4 MB L2 for the
 // whole pass over the rows — with all nb column tiles in flight (12 for c_fc: 4.7 MB of weights) the weights thrash it (L2 hit rate 69 %)
 __device__ __forceinline__ void g256_panel_order(unsigned lbid, int mt, int nb, int& mtile, int& nblk) {
-    constexpr int PANEL = G256_PANEL;
-    const int sn = PANEL <= 0 || nb <= PANEL ? nb : nb % PANEL == 0 ? PANEL : (PANEL >= 3 && nb % 3 == 0) ? 3 : (PANEL >= 2 && nb % 2 == 0) ? 2 : 1;
+    constexpr int PANEL = 4;                               // column tiles per panel
+    const int sn = nb <= PANEL ? nb : nb % PANEL == 0 ? PANEL : nb % 3 == 0 ? 3 : nb % 2 == 0 ? 2 : 1;
     const int per_panel = mt * sn;
     const int panel = (int)(lbid / (unsigned)per_panel);
     const int in_panel = (int)(lbid - (unsigned)panel * per_panel);

@@ -16,10 +16,6 @@ namespace {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VF_GEMM_X3H_TALL
-#define VF_GEMM_X3H_TALL 0     // A/B on the encoder's 1x1 shapes (tools/microbench.py gemm_1x1*): 143 vs 137, 164 vs 172, 180 vs 181 TF — a tie
-#endif
-
 constexpr int CK = 32;
 constexpr int BM = 128, BN = 128;
 constexpr int A_LDB = 144;                        // bytes per A row in LDS: 2 planes x 64 B + 16 B pad
@@ -44,11 +40,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x3h_kernel(vf_igemm_args p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // wave tile: TALL = all 128 rows x 32 columns (4 x 1 MFMA tiles) instead of 64 x 64 (2 x 2): no two waves stream the same weight
-    // fragment (half the weight bytes through the CU's vector-memory path; twice the A fragments from LDS, which has headroom)
-    constexpr bool TALL = VF_GEMM_X3H_TALL != 0;
-    constexpr int MI = TALL ? 4 : 2, NJ = TALL ? 1 : 2;
-    const int wave_m = TALL ? 0 : wave >> 1, wave_n = TALL ? wave : wave & 1;
+    // wave tile: 64 x 64 (2 x 2 MFMA tiles).  The tall 128 x 32 tile (no two waves stream the same weight fragment) measured a tie on the
+    // encoder's 1x1 shapes: 143 vs 137, 164 vs 172, 180 vs 181 TF
+    constexpr int MI = 2, NJ = 2;
+    const int wave_m = wave >> 1, wave_n = wave & 1;
     const int half = lane >> 5, l31 = lane & 31;
 
     const int nb = (p.Cout + BN - 1) / BN;

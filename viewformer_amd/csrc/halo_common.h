@@ -5,17 +5,7 @@
 #include "epilogue.h"
 #include "../../include/vf_hip.h"
 
-#ifndef VF_HALO_RES_PRELOAD
-#define VF_HALO_RES_PRELOAD 1   // residual values of all tiles fetched before the first store
-#endif
-#ifndef VF_GN_STATS_F64
-#define VF_GN_STATS_F64 1      // fused GroupNorm partial sums in fp64 (position-independent; 0: fp32, the round-1 form)
-#endif
-#if VF_GN_STATS_F64
-typedef double vf_gn_acc_t;
-#else
-typedef float vf_gn_acc_t;
-#endif
+typedef double vf_gn_acc_t;     // fused GroupNorm partial sums in fp64: position-independent (see vf_halo_epilogue_t)
 
 // MFMA row i (0..31) -> (tile row 0/1, pixel 0..15) such that each hardware ds_read_b128 16-lane group
 // ({0-3,12-15,20-27} / {4-11,16-19,28-31}) covers 16 CONSECUTIVE patch pixels
@@ -48,7 +38,7 @@ static inline int vf_halo_gn_check(const vf_igemm_args& a) {
 // the right half; with fp32 sums that made an image's GroupNorm statistics depend, in the last bit, on its position in the batch (the batch
 // invariance test held on its data until an unrelated epilogue change altered the compiler's fma contraction — tools/debug_invariance.py
 // found the layer).  The partial sums are therefore carried in fp64 (vf_gn_acc_t) and rounded once.
-template <bool PAIR, int MI, int NJ, bool PRELOAD = (VF_HALO_RES_PRELOAD != 0)>
+template <bool PAIR, int MI, int NJ, bool PRELOAD = true>
 __device__ __forceinline__ void vf_halo_epilogue_t(const vf_igemm_args& p, const f32x16 (&acc)[MI][NJ], int img, int img1, int y0,
                                                    int x0, int tile_slot, int nblk, int wave_m, int wave_n, int half, int l31) {
     constexpr int BN = 128;

@@ -50,23 +50,6 @@ __device__ __forceinline__ float vf_swish_1ulp(float v) {
     return v * r;
 }
 
-// the same function on two values with packed fp32 arithmetic (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two lanes of work per issue slot;
-// v_exp_f32 / v_rcp_f32 / v_min_f32 stay scalar).  Operation for operation the scalar sequence, so the results are its results bit for bit.
-typedef float vf_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ vf_f32x2 vf_swish_1ulp_pk(vf_f32x2 v) {
-    const vf_f32x2 LH = {-1.4426950408889634f, -1.4426950408889634f}, LL = {-1.9259629911266175e-8f, -1.9259629911266175e-8f};
-    const vf_f32x2 LN2 = {0.6931471805599453f, 0.6931471805599453f}, ONE = {1.0f, 1.0f};
-    vf_f32x2 th = v * LH;
-    const vf_f32x2 tl = __builtin_elementwise_fma(v, LH, -th) + v * LL;
-    th.x = fminf(th.x, 126.0f);
-    th.y = fminf(th.y, 126.0f);
-    const vf_f32x2 e0 = {__builtin_amdgcn_exp2f(th.x), __builtin_amdgcn_exp2f(th.y)};
-    const vf_f32x2 d = ONE + __builtin_elementwise_fma(e0 * tl, LN2, e0);
-    vf_f32x2 r = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-    r = __builtin_elementwise_fma(__builtin_elementwise_fma(-d, r, ONE), r, r);
-    return v * r;
-}
-
 __device__ __forceinline__ float vf_gelu_erf(float v) {
     // tf.nn.gelu(approximate=False): 0.5 x (1 + erf(x / sqrt 2))
     return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
@@ -234,17 +217,10 @@ __host__ __device__ __forceinline__ uint32_t vf_dropout_thresh(float rate) { ret
 // neighbours of one conv tile) would land in 8 different L2s and the tile would be fetched from HBM 8 times (measured on the bf16
 // GEMM 65536x768x3072: FETCH_SIZE 1.65 GB for 0.25 GB of operands).  Remap so that every XCD works on one contiguous range of
 // logical ids: XCD x owns the physical ids {x + 8 i}; it gets the logical range starting at x*q + min(x, r), q = n / 8, r = n % 8.
-#ifndef VF_XCD_SWIZZLE
-#define VF_XCD_SWIZZLE 1
-#endif
 __device__ __forceinline__ unsigned vf_xcd_bid() {
-#if VF_XCD_SWIZZLE
     const unsigned n = gridDim.x, b = blockIdx.x;
     const unsigned q = n >> 3, r = n & 7u, x = b & 7u, i = b >> 3;
     return x * q + (x < r ? x : r) + i;
-#else
-    return blockIdx.x;
-#endif
 }
 
 // sum of squares of four consecutive z values with a FIXED association and explicit fmas (no contraction freedom): the unit of the
@@ -255,102 +231,12 @@ __device__ __forceinline__ float vf_vq_sq4(const f32x4 v) {
 }
 
 // ---- build-flag registry (vf_build_flags / vf_build_flag_name, include/vf_hip.h) -------------------------------------------------
-// Developer switches that change RESULTS (ablations: a phase of a kernel compiled out) or make a kernel write debug data (cycle
-// stamps) live in the product sources behind -D macros.  Every translation unit built with one of them registers its name at load
-// time; a product build registers nothing, vf_build_flags() returns 0, and tests/test_abi.py asserts that of the shipped .so.
+// The one developer switch left in the product sources builds the compiler-ordered reference that tests compare the product with.  Every
+// translation unit built with it registers its name at load time; a product build registers nothing, vf_build_flags() returns 0, and
+// tests/test_abi.py asserts that of the shipped .so (and that no other macro is tested by a preprocessor conditional in csrc/).
 extern "C" int vf_register_build_flag(const char* name);
 #define VF_REG_FLAG(m) namespace { const int vf_flagreg_##m = vf_register_build_flag(#m); }
-#ifdef ADMA_X_NOCOMPUTE
-VF_REG_FLAG(ADMA_X_NOCOMPUTE)
-#endif
-#ifdef ADMA_X_NODMA
-VF_REG_FLAG(ADMA_X_NODMA)
-#endif
-#ifdef ADMA_X_NOSM
-VF_REG_FLAG(ADMA_X_NOSM)
-#endif
-#ifdef ADMA_STAMPS
-VF_REG_FLAG(ADMA_STAMPS)
-#endif
-#ifdef ATT_X_NOMFMA
-VF_REG_FLAG(ATT_X_NOMFMA)
-#endif
-#ifdef ATT_X_NOSTAGE
-VF_REG_FLAG(ATT_X_NOSTAGE)
-#endif
-#ifdef ATT_X_NOSOFTMAX
-VF_REG_FLAG(ATT_X_NOSOFTMAX)
-#endif
-#ifdef ATT_X_NOGLOBAL
-VF_REG_FLAG(ATT_X_NOGLOBAL)
-#endif
-#ifdef G256_A_VIA_REGS
-VF_REG_FLAG(G256_A_VIA_REGS)
-#endif
-#ifdef G256_STAMPS
-VF_REG_FLAG(G256_STAMPS)
-#endif
-#if defined(G256_PERSIST) && G256_PERSIST
-VF_REG_FLAG(G256_PERSIST)
-#endif
-#ifdef VQF_STAMPS
-VF_REG_FLAG(VQF_STAMPS)
-#endif
-#ifdef VQF_X_NORERANK
-VF_REG_FLAG(VQF_X_NORERANK)
-#endif
-#ifdef VQF_X_STAGGER
-VF_REG_FLAG(VQF_X_STAGGER)
-#endif
-#if defined(VF_W2_ABL) && VF_W2_ABL
-VF_REG_FLAG(VF_W2_ABL)
-#endif
-#if defined(VF_X3H_LDS_PAD) && VF_X3H_LDS_PAD
-VF_REG_FLAG(VF_X3H_LDS_PAD)
-#endif
-#if defined(VF_X3H16_ABL) && VF_X3H16_ABL
-VF_REG_FLAG(VF_X3H16_ABL)
-#endif
-#ifdef G256_X_K32PROBE
-VF_REG_FLAG(G256_X_K32PROBE)
-#endif
-#ifdef VF_X3H_STAMPS
-VF_REG_FLAG(VF_X3H_STAMPS)
-#endif
-#ifdef VF_X3H_X_NOPATCH
-VF_REG_FLAG(VF_X3H_X_NOPATCH)
-#endif
-#ifdef VF_X6_CLOCKPROBE
-VF_REG_FLAG(VF_X6_CLOCKPROBE)
-#endif
-#ifdef VF_X_DKV_HASH_PER_ELEMENT      // A/B: the dK / dV kernel's dropout words hashed by every lane (round 5's form) instead of once per lane quad
-VF_REG_FLAG(VF_X_DKV_HASH_PER_ELEMENT)
-#endif
-#ifdef VF_X_ATB_VISLOOP   // A/B: the backward attention kernels' tile lists from loops over visible()
-VF_REG_FLAG(VF_X_ATB_VISLOOP)
-#endif
-#ifdef VF_X_DKV_SEL2      // A/B: the dK / dV kernel's dropout with two selects per score (dP and P) instead of one
-VF_REG_FLAG(VF_X_DKV_SEL2)
-#endif
-#ifdef VF_X_DKV_ROT3      // A/B: the dK / dV kernel's mask rotation as shl / shr / or (before the third session of round 6)
-VF_REG_FLAG(VF_X_DKV_ROT3)
-#endif
-#if defined(ATB_ABL) && ATB_ABL      // ablation builds of the backward attention kernels (results wrong, timing only)
-VF_REG_FLAG(ATB_ABL)
-#endif
-#if defined(ATB_KV_UNI) && !ATB_KV_UNI      // A/B: rows image + tr image per streamed operand in the dK / dV kernel
-VF_REG_FLAG(ATB_KV_UNI)
-#endif
-#if defined(ATB_DQ_UNI) && !ATB_DQ_UNI      // A/B: K rows | V rows | K tr per slot in the dQ kernel
-VF_REG_FLAG(ATB_DQ_UNI)
-#endif
-#if defined(ADMA_REGROUP) && !ADMA_REGROUP    // A/B: four consecutive query views per workgroup under the streams mask
-VF_REG_FLAG(ADMA_REGROUP)
-#endif
-#if defined(ADMA_RING) && ADMA_RING != 4    // A/B: the forward DMA-ring attention with three slots
-VF_REG_FLAG(ADMA_RING)
-#endif
-#ifdef VF_X_TRINTRIN      // A/B: the transposing LDS reads through the compiler intrinsic again (hipcc then drains vmcnt in front of them)
+#ifdef VF_X_TRINTRIN      // the transposing LDS reads through the compiler intrinsic again (hipcc then drains vmcnt in front of them)
 VF_REG_FLAG(VF_X_TRINTRIN)
 #endif
 
@@ -375,13 +261,12 @@ static inline bool vf_attn_visible(int qv, int kv, int twin) {           // the 
     return kv == qv || (kv < Vc ? kv : Vc) < (qv < Vc ? qv : Vc);
 }
 // nblocks owner blocks of `vpb` views each over nviews views; by_key: the owners are KEY views (weight = query tiles that see one of them),
-// otherwise QUERY views (weight = key tiles one of them sees).  heaviest_first = false: the identity
-static inline vf_attn_order vf_attn_block_order(int nviews, int vpb, int nblocks, int twin, bool by_key, bool heaviest_first) {
+// otherwise QUERY views (weight = key tiles one of them sees)
+static inline vf_attn_order vf_attn_block_order(int nviews, int vpb, int nblocks, int twin, bool by_key) {
     vf_attn_order o;
     int w[64];
     if (nblocks > 64) nblocks = 64;
     for (int b = 0; b < 64; ++b) o.blk[b] = (unsigned char)b;
-    if (!heaviest_first) return o;
     for (int b = 0; b < nblocks; ++b) {
         int cnt = 0;
         for (int t = 0; t < nviews; ++t) {
@@ -405,19 +290,19 @@ static inline vf_attn_order vf_attn_block_order(int nviews, int vpb, int nblocks
 // CONSECUTIVE views are the right group under the causal and twin masks; under the training step's STREAMS mask (Sv views per stream, stream 0 = the
 // sequence, streams >= 1 = branch views that see the sequence's views below their own index plus themselves) they are not: branch view i of every
 // stream sees the same sequence views, so {stream 1 view i, stream 2 view i, stream 1 view i - 1, stream 2 view i - 1} shares i sequence tiles where four
-// consecutive views of one stream share i - 2 and walk i + 2.  Grouping (regroup = true, streams mask): the sequence's views four by four; a last
+// consecutive views of one stream share i - 2 and walk i + 2.  Grouping (streams mask): the sequence's views four by four; a last
 // partial group is topped up with the highest branch views; the branch views by descending index (all streams of an index together) four by four.
 // 3 x 10 views: 62 tile steps per (scene, head) instead of 75.  Every wave still walks ITS keys in ascending order: results are bit-identical.
 // Groups are dispatched heaviest first (as the blocks of vf_attn_block_order).  view = 0xFF: no view (the wave only helps moving tiles).
 struct vf_attn_groups { unsigned char view[64][4]; int n; };
-static inline vf_attn_groups vf_attn_query_groups(int nviews, int twin, bool regroup, bool heaviest_first) {
+static inline vf_attn_groups vf_attn_query_groups(int nviews, int twin) {
     vf_attn_groups g;
     for (int i = 0; i < 64; ++i) for (int j = 0; j < 4; ++j) g.view[i][j] = 0xFF;
     g.n = 0;
     unsigned char list[256];
     int nl = 0;
     const int Sv = twin <= -2 ? -twin : 0;
-    if (regroup && Sv > 0 && nviews % Sv == 0 && nviews / Sv >= 2 && nviews <= 255) {
+    if (Sv > 0 && nviews % Sv == 0 && nviews / Sv >= 2 && nviews <= 255) {
         const int NS = nviews / Sv;
         for (int v = 0; v < Sv; ++v) list[nl++] = (unsigned char)v;                       // the sequence's views, ascending
         const int pad = (4 - Sv % 4) % 4;                                                 // branch views that complete its last group
@@ -447,13 +332,12 @@ static inline vf_attn_groups vf_attn_query_groups(int nviews, int twin, bool reg
     }
     int ord[64];
     for (int b = 0; b < g.n; ++b) ord[b] = b;
-    if (heaviest_first)
-        for (int i = 1; i < g.n; ++i) {                                                   // stable insertion sort, descending weight
-            const int bi = ord[i];
-            int j = i - 1;
-            while (j >= 0 && w[ord[j]] < w[bi]) { ord[j + 1] = ord[j]; --j; }
-            ord[j + 1] = bi;
-        }
+    for (int i = 1; i < g.n; ++i) {                                                       // stable insertion sort, descending weight
+        const int bi = ord[i];
+        int j = i - 1;
+        while (j >= 0 && w[ord[j]] < w[bi]) { ord[j + 1] = ord[j]; --j; }
+        ord[j + 1] = bi;
+    }
     for (int b = 0; b < g.n; ++b) for (int j = 0; j < 4; ++j) g.view[b][j] = list[4 * ord[b] + j];
     return g;
 }

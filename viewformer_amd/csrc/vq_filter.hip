@@ -40,14 +40,9 @@ constexpr int KS = D / 16;
 constexpr int TN = 32;                 // codes per tile
 constexpr int TILE_BYTES = KS * 64 * 16;      // 16 KiB: [k-step][lane = half*32 + n][8 f16]
 constexpr int BM = 128;                // rows per workgroup (4 waves x 32)
-#ifndef VQF_NT
-#define VQF_NT 2                       // code tiles per step: independent accumulator chains per wave (one dependent chain leaves the
-#endif                                 // matrix pipe idle for the MFMA's result latency)
-#ifndef VQF_RING
-#define VQF_RING 2                     // LDS ring depth in steps (2: the next step lands while this one is multiplied)
-#endif
-constexpr int NT = VQF_NT;
-constexpr int RING = VQF_RING;
+constexpr int NT = 2;                  // code tiles per step: independent accumulator chains per wave (one dependent chain leaves the
+                                       // matrix pipe idle for the MFMA's result latency)
+constexpr int RING = 2;                // LDS ring depth in steps: the next step lands while this one is multiplied
 constexpr int STEP_BYTES = NT * TILE_BYTES;
 constexpr int PAIR_CAP = 192;          // (row, code) pairs per wave queued for the exact re-rank
 constexpr int MAX_KC = 1024;           // 10 code bits in the key
@@ -174,23 +169,6 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
     unsigned* wcnt = reinterpret_cast<unsigned*>(smem + OFF_WCNT);
     unsigned* scanrows = reinterpret_cast<unsigned*>(smem + OFF_SCAN);
 
-#ifdef VQF_STAMPS
-    unsigned long long stamp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define VQF_STAMP(i) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp[i]) :: "memory")
-#else
-#define VQF_STAMP(i)
-#endif
-    VQF_STAMP(0);
-#ifdef VQF_X_STAGGER      // experiment (round 4, tools/variants.sh): every second workgroup starts VQF_X_STAGGER cycles late, so that the two
-    if (blockIdx.x & 1) {  // workgroups of a CU are in different phases (z read / matrix loop / classification / re-rank) at any time
-        unsigned long long t0, t1;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0) :: "memory");
-        do {
-            __builtin_amdgcn_s_sleep(32);
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1) :: "memory");
-        } while (t1 - t0 < (unsigned long long)(VQF_X_STAGGER));
-    }
-#endif
     const Blob B = blob_view(blob_p, Kc);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
@@ -244,7 +222,6 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
         if (half == 0) eps_s[wr + l31] = eps_row;
     }
     __syncthreads();                                                                // every wave is done with R0: the ring may start
-    VQF_STAMP(1);
 
     // ---- codebook ring: a step = NT tiles of 32 codes; each wave moves a quarter (4 x 1 KiB) of every 16 KiB tile
     const int nsteps = ntiles / NT;                 // (Kc % (32 NT) == 0 is checked by the launcher)
@@ -258,7 +235,6 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
     };
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                 // nothing of this wave in flight: the ring owns vmcnt now
     issue_step(0);
-    if (RING > 2 && nsteps > 1) issue_step(1);
 
     float k1[16], k2[16], k3[16];
 #pragma unroll
@@ -279,12 +255,7 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
     auto step = [&](int t, f32x16 (&acc)[NT], const f32x16 (&prev)[NT]) {
         // lgkmcnt(0) too: the compiler leaves the last ds_reads of step t-1 in flight across the barrier (it only needs them at their
         // MFMA), and another wave's LDS-DMA for step t+RING-1 — issued right after ITS barrier — targets the buffer they read
-        if (RING > 2) {
-            if (t + 1 < nsteps) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * NT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        }
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                               // step t visible; everyone is done with step t-1
         if (t + RING - 1 < nsteps) issue_step(t + RING - 1);
         const unsigned char* bsrc = ring + (t % RING) * STEP_BYTES + lane * 16;
@@ -315,9 +286,7 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j) update_keys(accB[j], (unsigned)(((nsteps - 1) * NT + j) * TN + l31));
-    VQF_STAMP(2);
     __syncthreads();                                                                // ring is free: R0 becomes the re-rank's staging area
-    VQF_STAMP(6);
 
     // ---- candidates per row, through LDS atomics (a wave only touches its own 32 rows: wave-level ordering is enough).
     // Accumulator row r of a lane = row (r&3) + 8 (r>>2) + 4 half of the wave tile, column = l31.
@@ -373,7 +342,6 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
     const unsigned npairs_raw = wcnt[wave * 4 + 0], nscan = wcnt[wave * 4 + 1];
     const bool pair_overflow = npairs_raw > PAIR_CAP;                               // (needs > 6 candidates per row on average)
     const unsigned npairs = pair_overflow ? 0u : npairs_raw;
-    VQF_STAMP(3);
 
     // ---- exact re-rank of the queued (row, code) pairs.  The wave stages PAIRS_PER_PASS pairs' rows (z row, code row: coalesced
     // 1 KiB reads) into its slice of R0; lane p then runs pair p's fmaf chain out of LDS.
@@ -389,7 +357,6 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
             *reinterpret_cast<f32x4*>(my_r0 + p * PAIR_STRIDE + 1024 + lane * 16) = ev;
         }
         wave_sync();
-        if (p0 == 0) { VQF_STAMP(9); }
         if ((unsigned)lane < np) {
             const unsigned e = my_pairs[p0 + lane], rl = e >> 16, code = e & 0xFFFFu;
             const float d = exact_dist(reinterpret_cast<const float*>(my_r0 + lane * PAIR_STRIDE),
@@ -402,7 +369,6 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
         const unsigned long long best = rowbest[wr + lane];
         if (best != ~0ull) rowidx[wr + lane] = (int)(best & 0xFFFFFFFFull);
     }
-    VQF_STAMP(4);
     // ---- exact scan over every code for the rows the filter could not certify (and for all rows after a queue overflow)
     const unsigned nfull = pair_overflow ? 32u : nscan;
     for (unsigned s = 0; s < nfull; ++s) {
@@ -414,13 +380,6 @@ __global__ __launch_bounds__(256, 2) void vq_filter_kernel(const float* __restri
     }
     wave_sync();
     if (lane < 32 && m0 + lane < M) idx_out[m0 + lane] = (long long)rowidx[wr + lane];   // one coalesced 256-byte store per wave
-#ifdef VQF_STAMPS
-    VQF_STAMP(5);
-    if (stats && tid == 0 && blockIdx.x < 1024) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(stats + 4) + (size_t)blockIdx.x * 10;
-        for (int i = 0; i < 10; ++i) o[i] = stamp[i];
-    }
-#endif
     if (stats) {
         const unsigned s1 = n_single, s2 = n_amb;
         if (lane == 0) {
@@ -501,11 +460,7 @@ int vf_vq_argmin_filtered_f32(const float* z, const void* packed, int64_t M, int
     if (M == 0) return VF_OK;
     if (!z || !packed || !idx || M < 0 || Dd <= 0 || Kc <= 0) return VF_ERR_BAD_ARG;
     if (Dd != D || Kc % (2 * TN * NT) != 0 || Kc > MAX_KC) return VF_ERR_UNSUPPORTED;
-#ifdef VQF_ONE_PER_CU
-    const size_t smem = 100 * 1024;        // experiment: one workgroup per CU
-#else
     const size_t smem = SMEM_BYTES;
-#endif
     static unsigned long long attr_devs = 0;      // bit d: raised on device d (the attribute is per device)
     if (vf_attr_needed(&attr_devs)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vq_filter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
