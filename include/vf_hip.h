@@ -310,6 +310,19 @@ int vf_resize_u8(const uint8_t* src, uint8_t* dst, int n_img, int Hin, int Win, 
 size_t vf_image_metrics_workspace_bytes(int n_img, int H, int W, int C);
 int vf_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n_img, int H, int W, int C, int64_t* sums, double* ssim, void* workspace,
                         void* stream);
+/* camera k-nearest neighbours of the 7-Scenes pose refinement (viewformer/evaluate/evaluate_sevenscenes.py:36-45,188-189;
+ * csrc/camera_knn.hip): for each of Q query cameras (7 floats: xyz + quaternion w, x, y, z) the k cameras of db [N][7] with the smallest
+ *     pos_weight * ||xyz_db - xyz_q|| + 2 asin(|| vec(normalize(q_db) (x) conj(normalize(q_q))) ||)        (the reference: pos_weight 0.3)
+ * in ascending order, ties to the lowest index; idx [Q][k] (int32), dist [Q][k] the distances (may be NULL).  fp32 in the operation order
+ * of viewformer_amd/geometry.py; the asin argument is clamped to <= 1 (where the reference would give NaN).  Rows with a NaN distance
+ * sort last.  The result is a pure function of (db, query, k, pos_weight): selection is on the 64-bit keys (distance bits << 32) | index,
+ * independent of Q, tiling and grid.  1 <= k, k <= N, Q >= 0, finite pos_weight >= 0 and non-NULL db / queries / idx (workspace too
+ * when the query below is non-zero; 8-byte aligned), else VF_ERR_BAD_ARG; k > 32, N > 2^31 - 1 or Q > 524 280: VF_ERR_UNSUPPORTED; both
+ * before any launch.  Q == 0 is a no-op.  No allocation: per-tile candidates go to `workspace` (vf_camera_knn_workspace_bytes bytes; the
+ * query returns 0 for invalid shapes, and for N <= 1024 where a single launch writes the result). */
+size_t vf_camera_knn_workspace_bytes(int64_t N, int Q, int k);
+int vf_camera_knn_f32(const float* db, int64_t N, const float* queries, int Q, int k, float pos_weight, int32_t* idx, float* dist,
+                      void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Reduced-precision arm (bf16 MFMA, fp32 activations in HBM, fp32 accumulate / epilogue) for the layers whose

@@ -78,18 +78,20 @@ MAX_SCENES_PER_CALL = 256      # scenes per transformer / decoder pass: the refe
 
 
 def generate_batch_predictions(transformer_model, codebook_model, images, cameras, return_codes: bool = False,
-                               fused_passes: bool = True, max_scenes_per_call: int = None):
+                               fused_passes: bool = True, max_scenes_per_call: int = None, codes=None):
     """``fused_passes``: run the generation pass and the localization pass as one twin-view pass
     (MIGT.generate_and_localize; bit-identical rows, 8/14 of the transformer work at S=7); False = the
     reference's two separate calls.  Batches above ``max_scenes_per_call`` (default MAX_SCENES_PER_CALL) are processed in scene
-    chunks and concatenated."""
+    chunks and concatenated.  ``codes`` int [B,S,t,t]: the views' code maps when the caller already has them (scene_bank.SceneBank):
+    resize + encode are skipped and ``images`` [B,>=1,H,W,3] is read for ``ground_truth_images`` (its last view) only."""
     dev = codebook_model.device
     images = torch.as_tensor(images).to(dev)
     cameras = torch.as_tensor(cameras, dtype=torch.float32).to(dev)
     chunk = max_scenes_per_call or MAX_SCENES_PER_CALL
     if images.shape[0] > chunk:
         parts = [generate_batch_predictions(transformer_model, codebook_model, images[i:i + chunk], cameras[i:i + chunk], return_codes,
-                                            fused_passes, chunk) for i in range(0, images.shape[0], chunk)]
+                                            fused_passes, chunk, None if codes is None else codes[i:i + chunk])
+                 for i in range(0, images.shape[0], chunk)]
         # (a key that is None for a chunk — pose_last without localization — stays None: the schema does not depend on the batch size)
         return {k: (None if parts[0][k] is None else torch.cat([p[k] for p in parts])) for k in parts[0]}
     ground_truth_cameras = cameras[:, -1]
@@ -99,11 +101,16 @@ def generate_batch_predictions(transformer_model, codebook_model, images, camera
             cameras, transform = geometry.to_relative_cameras(cameras)
         cameras = geometry.normalize_cameras(cameras)                   # :102
 
-    B, S = images.shape[:2]
+    B, S = cameras.shape[:2]
     t = transformer_model.config.token_image_size
-    frames = _frames_for_encode(images, codebook_model.config.image_size)       # resize_tf inside encode(), :105
-    # encode every view, target included, exactly as the reference does (:114-116)
-    codes = codebook_model.encode(frames)[-1]
+    if codes is None:
+        frames = _frames_for_encode(images, codebook_model.config.image_size)   # resize_tf inside encode(), :105
+        # encode every view, target included, exactly as the reference does (:114-116)
+        codes = codebook_model.encode(frames)[-1]
+    else:
+        codes = torch.as_tensor(codes).to(dev)
+        if codes.numel() != B * S * t * t or images.shape[0] != B:
+            raise ValueError(f'codes {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
     codes = codes.to(torch.int32).view(B, S, t, t)                      # :110,116
 
     # ``return_codes`` also hands back the last view's logits; without it the arg-max is fused into the LM head's epilogue where the

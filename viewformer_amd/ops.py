@@ -703,3 +703,21 @@ def image_metrics_u8(a, b):
     ssim = torch.empty(n, dtype=torch.float64, device=a.device)
     check(lib.vf_image_metrics_u8(_p(a), _p(b), n, H, W, C, _p(sums), _p(ssim), _p(ws), _stream()), 'vf_image_metrics_u8')
     return sums, ssim
+
+
+def camera_knn(db, queries, k, pos_weight=0.3, return_dist=False):
+    """For each query camera [Q,7] the ``k`` cameras of ``db`` [N,7] (fp32, on the GPU) nearest in the pose distance of
+    viewformer/evaluate/evaluate_sevenscenes.py:36-45 (vf_camera_knn_f32): idx int32 [Q,k] ascending, ties to the lowest index; with
+    ``return_dist`` also the distances fp32 [Q,k].  1 <= k <= 32, k <= N.  One or two launches on the current stream, no synchronisation;
+    a query's row does not depend on the other queries of the call."""
+    if db.dim() != 2 or db.shape[1] != 7 or queries.dim() != 2 or queries.shape[1] != 7:
+        raise ValueError(f'camera_knn: db [N,7] and queries [Q,7] expected, got {tuple(db.shape)} and {tuple(queries.shape)}')
+    db = _f32(db, 'db').contiguous()
+    queries = _f32(queries, 'queries').contiguous()
+    N, Q, k = db.shape[0], queries.shape[0], int(k)
+    idx = torch.empty((Q, k), dtype=torch.int32, device=db.device)
+    dist = torch.empty((Q, k), dtype=torch.float32, device=db.device) if return_dist else None
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.vf_camera_knn_workspace_bytes(N, Q, k)), 8), dtype=torch.uint8, device=db.device)
+    check(lib.vf_camera_knn_f32(_p(db), N, _p(queries), Q, k, float(pos_weight), _p(idx), _p(dist), _p(ws), _stream()), 'vf_camera_knn_f32')
+    return (idx, dist) if return_dist else idx
