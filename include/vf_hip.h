@@ -255,6 +255,23 @@ int vf_attn_blockcausal_fp8(const void* q, const void* k, const void* v, int in_
 int vf_attn_blockcausal_x6(const float* q, const float* k, const float* v, float* out,
                            int B, int H, int T, int L, int ldq, int ldk, int ldv, int ldo,
                            float scale, int skip_masked, int twin_view, void* stream);
+/* Prefix-cache attention of the novel-view renderer (csrc/attention_prefix.hip; MIGT.prefill_context / generate_from_context): N independent
+ * query views per scene, rows [B*N*L] of q / k / v / out (thirds of the fused c_attn output in place: ld* in elements), each attending to
+ * the C*L cached keys of its scene — kp / vp, rows [C*L] with leading dimensions ldkp / ldvp, scene b at element offset b * prefix_stride —
+ * and to the L keys of its own view, nothing else: the visibility of a twin view of vf_attn_blockcausal_* (twin_view = C) for any number
+ * of alternative endings, without recomputing the prefix.  Un-scaled scores, fp32 softmax, no mask arithmetic (the keys a query does not
+ * walk are those whose weight is an exact zero).  A workgroup serves 4 (bf16) / 2 (f32eq) consecutive views of one (scene, head) and stages
+ * each prefix tile into LDS once for them; a query's result does not depend on N or on its position (bit-identical).
+ *   vf_attn_prefix_bf16:  bf16 MFMA; in_bf16: q / k / v / kp / vp are bf16 (ld*, prefix_stride % 8) or fp32 (% 4); out_bf16 as above.
+ *   vf_attn_prefix_f32eq: fp32-equivalent (x6 splitting as vf_attn_blockcausal_x6), fp32 everywhere.
+ * L = 64 and dh = 64 (head dimension), C >= 1: anything else VF_ERR_UNSUPPORTED before any launch; NULL pointers, ld* < H * 64 or
+ * misaligned: VF_ERR_BAD_ARG; B = 0 or N = 0: no-op, VF_OK. */
+int vf_attn_prefix_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
+                        int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                        int ldo, void* stream);
+int vf_attn_prefix_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
+                         int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                         int ldo, void* stream);
 /* Single-head spatial self-attention of the VQGAN AttnBlock, fused (csrc/attn_spatial.hip): replaces the core of AttnBlock.forward
  * (vqgan_th.py:124-141) — scores = q^T k * scale, softmax over the keys, h = v . p^T — per image of HW tokens x C channels, from the
  * fused q|k|v projection qkv [n_img * HW][ld] (q at column 0, k at C, v at 2C); out [n_img * HW][ldo].  Exact fp32

@@ -29,6 +29,29 @@ class _Dense:
     __slots__ = ('wp', 'wp16', 'wp6', 'bias', 'k', 'n', 'w_raw')
 
 
+class ContextCache:
+    """Keys and values of C context views in every layer (MIGT.prefill_context): ``kv[i]`` is layer i's fused c_attn output
+    [B*C*L, 3*d_model] with thirds (V, Q, K).  Valid for the model object, weights, arithmetic arm and device that made it."""
+    __slots__ = ('kv', 'B', 'C', 'tshape', 'device', 'arm', 'act16', 'qkv16', '_owner', '_weights')
+
+    def __init__(self, model, kv, B, C, tshape):
+        import weakref
+        self.kv, self.B, self.C, self.tshape = kv, B, C, tuple(tshape)
+        self.device = model.device
+        self.arm = (model.precision, model.dense_arith, model.attention)
+        self.act16, self.qkv16 = model._act_dtypes()
+        self._owner = weakref.ref(model)
+        self._weights = model._weights_version
+
+    def check(self, model):
+        if self._owner() is not model or self._weights != model._weights_version:
+            raise ValueError('ContextCache belongs to another model (or to weights that have been replaced since): prefill again')
+        if self.arm != (model.precision, model.dense_arith, model.attention) or (self.act16, self.qkv16) != model._act_dtypes():
+            raise ValueError(f'ContextCache was filled on the {self.arm} arm, the model now runs {(model.precision, model.dense_arith, model.attention)}')
+        if self.device != model.device:
+            raise ValueError(f'ContextCache lives on {self.device}, the model on {model.device}')
+
+
 class MIGT:
     def __init__(self, config: MIGTConfig = None, device=None, skip_masked: bool = True, precision: str = 'f32',
                  dense_arith: str = 'x3h', bf16_activations: bool = True, attention: str = None):
@@ -62,6 +85,7 @@ class MIGT:
         self._sd_host = None
         self._dense = {}
         self._ln = {}
+        self._weights_version = 0                             # counts uploads: a ContextCache is tied to the weights that filled it
 
     def eval(self):
         return self
@@ -163,6 +187,7 @@ class MIGT:
             for p in ('attn.c_attn', 'attn.c_proj', 'mlp.c_fc', 'mlp.c_proj'):
                 dense(f'h.{i}.{p}')
         ln('ln_f')
+        self._weights_version += 1
         torch.cuda.synchronize(dev)
 
     # ------------------------------------------------------------------ helpers
@@ -217,31 +242,43 @@ class MIGT:
                                       # keys and values of the next block), the last block's other rows feed nothing.  Row for row the same launches on fewer
                                       # rows (GEMM rows, LayerNorm rows are independent of each other): the rows that are returned keep their bits
 
-    def _blocks(self, ids, add_emb, B, V, L, mask_spec=-1, tail_views=0):
+    def _act_dtypes(self):
+        """(act16, qkv16): whether LayerNorm / GELU / attention outputs, and the fused c_attn output, are bf16 tensors in this arm"""
+        c = self.config
+        d = c.d_model
+        l0 = self._dense['h.0.mlp.c_proj'] if c.n_layer else None
+        act16 = (self.precision == 'bf16' and self.bf16_activations and d % 128 == 0 and l0 is not None and l0.k % 128 == 0
+                 and all(self._dense[f'h.{i}.{n}'].wp16 is not None for i in range(c.n_layer)
+                         for n in ('attn.c_attn', 'attn.c_proj', 'mlp.c_fc', 'mlp.c_proj')))
+        # the fused c_attn output is bf16 too (bit-identical downstream: the attention kernel rounds fp32 q/k/v to bf16 on load): half
+        # the bytes written by the GEMM and read by the attention, whose LDS-DMA kernel (attention_dma.hip) takes bf16 tiles straight
+        # into LDS.  VF_QKV16=0 keeps fp32 q/k/v (A/B runs).
+        # (the fp8 arm's kernel stages its tiles through registers and takes fp32 q/k/v at full speed: no bf16 there)
+        qkv16 = act16 and self.attention != 'fp8' and os.environ.get('VF_QKV16', '1') != '0'
+        return act16, qkv16
+
+    def _blocks(self, ids, add_emb, B, V, L, mask_spec=-1, tail_views=0, kv_sink=None):
         """embedding sum -> n_layer x Block -> ln_f over V views of L tokens.  ids [B,V,...] int,
         add_emb [B,V,d] (pose embedding or LOC-token row per view).  Returns [B*V*L, d]; with ``tail_views`` = k > 0 (and prune_last_block)
-        the hidden states of the last k views only, [B*k*L, d]."""
+        the hidden states of the last k views only, [B*k*L, d].  ``kv_sink``: a list that receives every layer's fused c_attn output
+        [B*V*L, 3d] (thirds V, Q, K), each in a buffer of its own."""
         c, dev = self.config, self.device
         d, H = c.d_model, c.n_head
         T, M = V * L, B * V * L
         add = add_emb.contiguous().view(B * V, d)
         ids32 = ids.reshape(M).to(torch.int32).contiguous()
         h = ops.embed_sum(ids32, self._wte, self._wpe, add, B * V, L, d, c.n_embeddings + 2)   # migt.py:392
-        l0 = self._dense['h.0.mlp.c_proj'] if c.n_layer else None
-        act16 = (self.precision == 'bf16' and self.bf16_activations and d % 128 == 0 and l0 is not None and l0.k % 128 == 0
-                 and all(self._dense[f'h.{i}.{n}'].wp16 is not None for i in range(c.n_layer)
-                         for n in ('attn.c_attn', 'attn.c_proj', 'mlp.c_fc', 'mlp.c_proj')))
+        act16, qkv16 = self._act_dtypes()
         att = torch.empty((M, d), dtype=torch.bfloat16 if act16 else torch.float32, device=dev)
-        # the fused c_attn output is bf16 too (bit-identical downstream: the attention kernel rounds fp32 q/k/v to bf16 on load): half
-        # the bytes written by the GEMM and read by the attention, whose LDS-DMA kernel (attention_dma.hip) takes bf16 tiles straight
-        # into LDS.  VF_QKV16=0 keeps fp32 q/k/v (A/B runs).
-        # (the fp8 arm's kernel stages its tiles through registers and takes fp32 q/k/v at full speed: no bf16 there)
-        qkv16 = act16 and self.attention != 'fp8' and os.environ.get('VF_QKV16', '1') != '0'
         qkv = torch.empty((M, 3 * d), dtype=torch.bfloat16 if qkv16 else torch.float32, device=dev)
         for i in range(c.n_layer):                                           # Block.call, migt.py:230-238
             p = f'h.{i}'
             a = ops.layernorm(h, *self._ln[p + '.ln_1'], M, d, out_bf16=act16)
             ca = self._dense[p + '.attn.c_attn']
+            if kv_sink is not None:                                          # prefill_context: every layer keeps its c_attn output (the K / V cache)
+                if i:
+                    qkv = torch.empty_like(qkv)
+                kv_sink.append(qkv)
             self._dense_launch(a, ca, M, qkv)
             # thirds are (V, Q, K): migt.py:207-213
             ops.attn_blockcausal(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], att, B, H, T, L,
@@ -262,6 +299,84 @@ class MIGT:
             h = h.view(B, V, L, d)[:, V - tail_views:].reshape(B * tail_views * L, d)
             M = B * tail_views * L
         return ops.layernorm(h, *self._ln['ln_f'], M, d)                    # migt.py:408
+
+    # ------------------------------------------------------------------ many novel views from one context (prefix cache)
+    def _check_render_shapes(self, L):
+        c = self.config
+        if self._sd_host is None or self.device is None:
+            raise RuntimeError('MIGT: load_state_dict() and .to("cuda") first')
+        if self.attention == 'fp8':
+            raise ops._lib.VfError("the prefix-cache attention has a bf16 and an fp32-equivalent arm: attention='fp8' is not supported")
+        if c.d_model // c.n_head != 64 or c.d_model % c.n_head or L != 64:
+            raise ops._lib.VfError(f'prefix-cache attention supports head dim 64 and 64-token views only (got head dim '
+                                   f'{c.d_model // c.n_head}, {L} tokens)')
+
+    def prefill_context(self, codes, cameras):
+        """Run the C context views once and keep every layer's keys and values: ``codes`` int [B,C,t,t], ``cameras`` fp32 [B,C,7]
+        (relative + normalised) -> ContextCache for ``generate_from_context``.  Block-causal attention never shows a context view the
+        target, ``wpe`` indexes the token inside a view and the poses are relative to view 0, so the context's hidden states — and each
+        layer's K / V for them — do not depend on the query.  The cache IS each layer's fused c_attn output (thirds V, Q, K; the Q
+        third is not read again): no copy, dtype as the arm's ``qkv``."""
+        codes = torch.as_tensor(codes).to(self.device)
+        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.device)
+        if codes.dim() < 3 or cameras.shape[:2] != codes.shape[:2] or cameras.shape[-1] != 7 or codes.shape[1] < 1:
+            raise ValueError(f'prefill_context: codes [B,C,t,t] and cameras [B,C,7] expected, got {tuple(codes.shape)} and {tuple(cameras.shape)}')
+        B, C = codes.shape[:2]
+        tshape = tuple(codes.shape[2:])
+        L = int(np.prod(tshape))
+        self._check_render_shapes(L)
+        kv = []
+        self._blocks(codes, self._pose_embed(cameras), B, C, L, kv_sink=kv)
+        return ContextCache(self, kv, B, C, tshape)
+
+    def generate_from_context(self, cache, query_cameras, codes_only: bool = True):
+        """N novel views per scene from a prefilled context: ``query_cameras`` fp32 [B,N,7] in the context's (relative, normalised)
+        frame -> generated code maps int64 [B,N,t,t], or with ``codes_only=False`` the logits [B,N,t,t,n_embeddings].  Every query is
+        a MASK view with its pose embedding — the last view of ``model(dict(input_ids=[ctx, MASK], poses=[ctx, query]))`` — whose
+        rows go through the same LayerNorm / dense launches as there (on B*N*L rows) and whose attention reads the context's keys and
+        values from the cache (ops.attn_prefix).  Queries are independent of each other: a query's rows do not depend on N."""
+        if not isinstance(cache, ContextCache):
+            raise TypeError('generate_from_context: a ContextCache from prefill_context expected')
+        cache.check(self)
+        c, dev = self.config, self.device
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
+        B, C, tshape = cache.B, cache.C, cache.tshape
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
+            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        L = int(np.prod(tshape))
+        self._check_render_shapes(L)
+        d, H, nE = c.d_model, c.n_head, c.n_embeddings
+        M = B * N * L
+        if N == 0:
+            return (torch.empty((B, 0, *tshape), dtype=torch.int64, device=dev) if codes_only
+                    else torch.empty((B, 0, *tshape, nE), dtype=torch.float32, device=dev))
+        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
+        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
+        h = ops.embed_sum(ids32, self._wte, self._wpe, add, B * N, L, d, nE + 2)           # migt.py:392
+        act16, qkv16 = cache.act16, cache.qkv16
+        att = torch.empty((M, d), dtype=torch.bfloat16 if act16 else torch.float32, device=dev)
+        qkv = torch.empty((M, 3 * d), dtype=torch.bfloat16 if qkv16 else torch.float32, device=dev)
+        for i in range(c.n_layer):                                           # Block.call on the query rows, migt.py:230-238
+            p = f'h.{i}'
+            a = ops.layernorm(h, *self._ln[p + '.ln_1'], M, d, out_bf16=act16)
+            self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
+            ckv = cache.kv[i]                                                # [B*C*L, 3d], thirds (V, Q, K)
+            ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
+                            3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16')
+            h = self._gemm(att, p + '.attn.c_proj', M, res=h)
+            m = ops.layernorm(h, *self._ln[p + '.ln_2'], M, d, out_bf16=act16)
+            f = self._gemm(m, p + '.mlp.c_fc', M, epilogue=ops.EPI_GELU, out_bf16=act16)
+            h = self._gemm(f, p + '.mlp.c_proj', M, res=h)
+        hf = ops.layernorm(h, *self._ln['ln_f'], M, d)                       # migt.py:408
+        gen = self._lm_argmax(hf, M) if codes_only else None
+        if gen is None:
+            lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
+            self._lm(hf, M, lg)                                              # migt.py:417
+            if not codes_only:
+                return lg.view(B, N, *tshape, nE)
+            gen = ops.argmax_rows(lg, M, nE)
+        return gen.view(B, N, *tshape)
 
     def generate_and_localize(self, codes, cameras, codes_only: bool = False):
         """The evaluator's two transformer passes (evaluate_transformer.py:119-123 and :134-136) as ONE pass.

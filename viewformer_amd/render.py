@@ -1,0 +1,152 @@
+"""Novel-view rendering: many query views from ONE context, without target frames.
+
+``evaluate.generate_batch_predictions`` is the evaluator's loop body: S views in, one view out, and it wants an image for the view it is
+about to generate.  An orbit of N views around C photographs costs it N * (C + 1) encoder passes and N * (C + 1) transformer views.  The
+model allows the saving exactly: the context views never see the target, so their encoder codes and every layer's keys
+and values are computed once (``MIGT.prefill_context``) and each query is a single MASK view attending to that cache
+(``MIGT.generate_from_context`` -> ``ops.attn_prefix``): C encodes, C context views, N query views, N decodes.
+
+    r = ViewRenderer(transformer_model, codebook_model)
+    r.set_context(images=frames_u8, cameras=cams)            # or codes=... (scene_bank.SceneBank.gather)
+    out = r.render(query_cameras)                            # out['generated_images'] uint8 [B,N,H,W,3]
+
+Contract: ``render(q)['generated_images'][b, n]`` is what ``generate_batch_predictions`` generates for the scene (context views of b...,
+any frame) with cameras (context cameras of b..., q[b, n]).
+
+Not covered here: localization from the cache (the LOC view needs the target's codes) and the multi-context ``evaluate_sequence``
+path; both keep their evaluators.
+"""
+import torch
+
+from . import geometry
+from . import ops
+from .evaluate import MAX_SCENES_PER_CALL, _frames_for_encode
+
+
+def context_poses(context_cameras, augment_poses: str):
+    """The context's model poses and the transform that made them: cameras [B,C,7] in the caller's world frame ->
+    (poses [B,C,7], transform [B,1,7] or None) — ``to_relative_cameras`` (relative to view 0) when the model was trained with
+    ``augment_poses == 'relative'``, then ``normalize_cameras``: evaluate_transformer.py:99-102."""
+    transform = None
+    if augment_poses == 'relative':
+        context_cameras, transform = geometry.to_relative_cameras(context_cameras)
+    return geometry.normalize_cameras(context_cameras), transform
+
+
+def query_poses(query_cameras, transform):
+    """Query cameras [B,N,7] in the caller's world frame -> model poses [B,N,7] in the context's frame.  ``transform``: view 0's camera
+    [B,1,7] from ``context_poses`` (None: no relativisation).  Equal, bit for bit, to the last camera of
+    ``normalize_cameras(to_relative_cameras(cat(context, query_n)))`` for every n: both relativise with view 0's camera, camera by
+    camera (tests/test_render_host.py)."""
+    if transform is not None:
+        # to_relative_cameras reads its transform from the first camera of the sequence: put view 0 in front, drop it afterwards
+        query_cameras = geometry.to_relative_cameras(torch.cat([transform, query_cameras], -2))[0][..., 1:, :]
+    return geometry.normalize_cameras(query_cameras)
+
+
+def default_views_per_call(n_scenes: int) -> int:
+    """Query views per scene in one transformer pass: at most MAX_SCENES_PER_CALL view-rows over the batch, the evaluator's own cap
+    (one query view has the activations of one of its scenes' views; the cap keeps every activation below 32-bit offsets)."""
+    return max(1, MAX_SCENES_PER_CALL // max(1, n_scenes))
+
+
+def plan_view_chunks(n_views: int, n_scenes: int = 1, max_views_per_call: int = None):
+    """[(start, stop)) ranges over the N query views of every scene: whole views, in order, each view exactly once, at most
+    ``max_views_per_call`` (default ``default_views_per_call(n_scenes)``) per range; [] for N = 0.  Pure: no device, no model."""
+    cap = default_views_per_call(n_scenes) if max_views_per_call is None else int(max_views_per_call)
+    if cap < 1 or n_views < 0:
+        raise ValueError(f'plan_view_chunks: max_views_per_call >= 1 and n_views >= 0 expected, got {cap} and {n_views}')
+    return [(a, min(a + cap, n_views)) for a in range(0, n_views, cap)]
+
+
+class ViewRenderer:
+    def __init__(self, transformer_model, codebook_model):
+        self.transformer = transformer_model
+        self.codebook = codebook_model
+        self.cache = None
+        self.transform = None
+        self.context_codes = None
+
+    def set_context(self, images=None, cameras=None, codes=None):
+        """``images`` uint8 [B,C,H,W,3] (host or device; resized for the encoder as the evaluators do) or ``codes`` int [B,C,t,t]
+        (already encoded, e.g. ``SceneBank.gather``), and ``cameras`` [B,C,7] in the caller's world frame.  Encodes once, prefills the
+        transformer's key / value cache once."""
+        tm, cm = self.transformer, self.codebook
+        dev = cm.device
+        if cameras is None or (images is None) == (codes is None):
+            raise ValueError('set_context: cameras and exactly one of images / codes expected')
+        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(dev)
+        if cameras.dim() != 3 or cameras.shape[-1] != 7 or cameras.shape[1] < 1:
+            raise ValueError(f'set_context: cameras [B,C,7] expected, got {tuple(cameras.shape)}')
+        B, C = cameras.shape[:2]
+        t = tm.config.token_image_size
+        poses, transform = context_poses(cameras, tm.config.augment_poses)
+        if codes is None:
+            images = torch.as_tensor(images).to(dev)
+            if images.dim() != 5 or tuple(images.shape[:2]) != (B, C):
+                raise ValueError(f'set_context: images [B,C,H,W,3] with one frame per camera of {tuple(cameras.shape)} expected, got {tuple(images.shape)}')
+            codes = cm.encode(_frames_for_encode(images, cm.config.image_size))[-1]
+        else:
+            codes = torch.as_tensor(codes).to(dev)
+            if codes.numel() != B * C * t * t:
+                raise ValueError(f'set_context: codes {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
+        codes = codes.to(torch.int32).view(B, C, t, t)
+        self.cache = tm.prefill_context(codes, poses)
+        self.transform, self.context_codes = transform, codes
+        return self
+
+    def render(self, query_cameras, max_views_per_call: int = None, return_codes: bool = False):
+        """``query_cameras`` [B,N,7] in the caller's world frame (the context's) -> dict(generated_images uint8 [B,N,H,W,3]); with
+        ``return_codes`` also generated_codes int64 [B,N,t,t], logits fp32 [B,N,t,t,n_embeddings] and decoded (the decoder's fp32
+        output [B,N,H,W,3]).  N is walked in chunks of whole views (``plan_view_chunks``); a view's result does not depend on the
+        chunking."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.render: set_context() first')
+        tm, cm = self.transformer, self.codebook
+        dev = cm.device
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
+        B = self.cache.B
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
+            raise ValueError(f'render: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        t = tm.config.token_image_size
+        nE = tm.config.n_embeddings
+        poses = query_poses(query_cameras, self.transform)
+        gen, lgs = [], []
+        for a, b in plan_view_chunks(N, B, max_views_per_call):
+            if return_codes:
+                lg = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=False)
+                lgs.append(lg)
+                gen.append(ops.argmax_rows(lg.view(-1, nE), B * (b - a) * t * t, nE).view(B, b - a, t, t))   # ties -> lowest index
+            else:
+                gen.append(tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True))
+        codes = torch.cat(gen, 1) if gen else torch.empty((B, 0, t, t), dtype=torch.int64, device=dev)
+        flat = codes.reshape(B * N, t, t)
+        decs, imgs = [], []
+        for a in range(0, B * N, MAX_SCENES_PER_CALL):
+            dec = cm.decode_code(flat[a:a + MAX_SCENES_PER_CALL])
+            if cm.data_format == 'NCHW':
+                dec = dec.permute(0, 2, 3, 1)
+            dec = dec.contiguous()
+            imgs.append(ops.postprocess_u8(dec))
+            if return_codes:
+                decs.append(dec)
+        if imgs:
+            img = torch.cat(imgs) if len(imgs) > 1 else imgs[0]
+        else:
+            s = cm.config.image_size
+            img = torch.empty((0, s, s, 3), dtype=torch.uint8, device=dev)
+        res = dict(generated_images=img.view(B, N, *img.shape[1:]))
+        if return_codes:
+            dec = torch.cat(decs) if len(decs) > 1 else (decs[0] if decs else torch.empty((0, *img.shape[1:]), dtype=torch.float32, device=dev))
+            res.update(generated_codes=codes,
+                       logits=torch.cat(lgs, 1) if lgs else torch.empty((B, 0, t, t, nE), dtype=torch.float32, device=dev),
+                       decoded=dec.view(B, N, *dec.shape[1:]))
+        return res
+
+
+def render_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.render``'s
+    dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``max_views_per_call``, ``return_codes``."""
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    return r.render(query_cameras, **kw)
