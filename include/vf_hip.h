@@ -23,6 +23,23 @@
  *     products — the default of the inference encoder); they differ from the fp32
  *     reference by summation order only.  *_bf16 / *_fp8 entry points round
  *     their operands once and are the tolerance arms.
+ *
+ * Memory footprint (every entry point; tests/test_hip_bounds.py checks it on framed buffers,
+ * DESIGN.md 5).  No buffer here is bounds-checked by the hardware, outputs are column slices
+ * of wider buffers and a tensor's neighbour is another live tensor, so:
+ *   1. Writes.  For an output of `rows` x `cols` elements with row stride `ld`, a kernel writes
+ *      only the elements [r][c] with r < rows and c < cols, and it writes every one of them
+ *      (accumulating outputs — "(+)=", "+=", counters — are read-modify-written instead).  It never
+ *      writes the ld - cols gap behind a row, anything before the first or after the last
+ *      element, or — between batch entries or split-K slabs — the stride_out - rows*ld gap.
+ *      A workspace is written only inside [0, vf_*_workspace_bytes(...)) (or the size the entry
+ *      point states: vf_l1_loss_partials, vf_lpips_head_blocks, vf_dense_small_n_wgrad_slabs,
+ *      vf_conv3_wgrad_x6_rows, vf_conv3_halo_gn_slots), inputs are never written.
+ *   2. Reads.  The outputs are a function of the LOGICAL elements of the inputs only: the bytes
+ *      in the gaps, before, after or between the inputs may hold anything (NaN, +-3e38) without
+ *      changing one output bit.  A kernel may still load such bytes (a ragged last tile), so
+ *      they must be mapped — which they are wherever the gap lies inside the caller's buffer.
+ *   No entry point is excepted from either clause.
  */
 #ifndef VF_HIP_H
 #define VF_HIP_H

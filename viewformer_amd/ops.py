@@ -329,7 +329,7 @@ def igemm(x, w_packed, M, Cin, Cout, out, bias=None, res=None, mode=MODE_GEMM, e
     a.out = out.data_ptr()
     if out_aux is not None:
         _chk(out_aux, torch.bfloat16, 'out_aux')
-        if out_aux.shape != out.shape or not out_aux.is_contiguous():
+        if out_aux.shape != out.shape or not (out_aux.is_contiguous() or out_aux.stride() == out.stride()):
             raise _lib.VfError('out_aux must have the shape and row stride of out')
         a.out_aux = out_aux.data_ptr()
     if pro is not None:
