@@ -453,10 +453,12 @@ int vf_conv3_wgrad_x6(const float* x, const void* dy_packed, float* slabs, int n
                       int Cout, int mode, int splits, void* stream);
 /* nearest-x2 upsample backward (Upsample.forward vqgan_th.py:29-32): dx = 2x2 block sums of du [n][2H][2W][C] */
 int vf_upsample2_bwd_f32(const float* du, float* dx, int n_img, int H, int W, int C, void* stream);
-/* GroupNorm(+swish) backward (Normalize / nonlinearity vqgan_th.py:11-17): dx (+=), chan_sums [n_img][C][2] = {dgamma, dbeta} parts */
+/* GroupNorm(+swish) backward (Normalize / nonlinearity vqgan_th.py:11-17): dx (+=), chan_sums [n_img][C][2] = {dgamma, dbeta} parts.
+ * mean_c / scale_c: the forward's (vf_groupnorm_stats_f32), eps: the forward's.  Gains may be zero or denormal: rstd is taken per
+ * (image, group) from the channel of largest |scale_c|, and from the group's own variance (with eps) where all its gains vanish. */
 size_t vf_groupnorm_bwd_workspace_bytes(int n_img, int HW, int C, int groups);
 int vf_groupnorm_bwd_f32(const float* x, const float* da, const float* mean_c, const float* scale_c, const float* gamma,
-                         const float* beta, float* dx, float* chan_sums, int n_img, int HW, int C, int groups, int swish,
+                         const float* beta, float* dx, float* chan_sums, int n_img, int HW, int C, int groups, float eps, int swish,
                          int accumulate, void* ws, void* stream);
 /* row softmax backward (AttnBlock vqgan_th.py:132-134): dp <- scale * p * (dp - sum p dp) in place */
 int vf_softmax_rows_bwd_f32(const float* p, float* dp, int64_t rows, int n, float scale, void* stream);
@@ -637,11 +639,14 @@ int vf_adamw_flat_pack_f32(float* param, const float* grad, float* m, float* v, 
 int vf_add_inplace_f32(float* a, const float* b, int64_t n, void* stream);
 /* out = a*x + b*y (y may be NULL: out = a*x); out may alias x or y */
 int vf_axpby_f32(float a, const float* x, float b, const float* y, float* out, int64_t n, void* stream);
-/* tf.clip_by_norm per tensor (migt.py:486-487): x *= clip / max(||x||, clip); scratch1 = one float */
-int vf_clip_by_norm_f32(float* x, int64_t n, float clip, float* scratch1, void* stream);
+/* scratch of the two clip entry points: vf_clip_scratch_floats() floats (per-block partial sums of squares, added in a fixed order:
+ * the clip factor is bit-reproducible).  The contents need no initialisation and are not preserved. */
+int vf_clip_scratch_floats(void);
+/* tf.clip_by_norm per tensor (migt.py:486-487): x *= clip / max(||x||, clip) */
+int vf_clip_by_norm_f32(float* x, int64_t n, float clip, float* scratch, void* stream);
 /* global-norm clip of a flat gradient buffer as pytorch_lightning's Trainer(gradient_clip_val=...) applies it to the codebook model
  * (train_codebook_th.py:69 -> torch.nn.utils.clip_grad_norm_): x *= max_norm / (||x|| + 1e-6) when that factor is < 1 */
-int vf_clip_grad_norm_f32(float* x, int64_t n, float max_norm, float* scratch1, void* stream);
+int vf_clip_grad_norm_f32(float* x, int64_t n, float max_norm, float* scratch, void* stream);
 
 #ifdef __cplusplus
 }

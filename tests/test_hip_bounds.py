@@ -743,7 +743,7 @@ def _gn_bwd(HW):
         def fn(A):
             dx, chan = A.out('dx', (n * HW, C)), A.out('chan_sums', (n, 2 * C))
             _ok(_lib_().vf_groupnorm_bwd_f32(_P(A.inp('x', x)), _P(A.inp('da', da)), _P(A.inp('mean_c', mean)), _P(A.inp('scale_c', scale)),
-                                             _P(A.inp('gamma', gamma)), _P(A.inp('beta', beta)), _P(dx), _P(chan), n, HW, C, 32, 1, 0, _P(A.ws('ws', nws)),
+                                             _P(A.inp('gamma', gamma)), _P(A.inp('beta', beta)), _P(dx), _P(chan), n, HW, C, 32, 1e-6, 1, 0, _P(A.ws('ws', nws)),
                                              _strm()), 'vf_groupnorm_bwd_f32')
             return {'dx': dx, 'chan_sums': chan}
         return fn

@@ -156,7 +156,7 @@ def lib():
 def test_camera_knn_abi_validation_without_gpu(lib):
     d = ctypes.c_void_p(4096)              # never dereferenced
     knn, ws = lib.vf_camera_knn_f32, lib.vf_camera_knn_workspace_bytes
-    assert lib.vf_abi_version() == 19      # the addition is additive
+    assert lib.vf_abi_version() == 20      # the addition is additive
     assert knn(d, 7000, d, 4, 0, 0.3, d, d, d, None) == -1             # k = 0
     assert knn(d, 7000, d, 4, 33, 0.3, d, d, d, None) == -2            # k = 33: unsupported
     assert knn(d, 8, d, 4, 9, 0.3, d, d, d, None) == -1                # N < k

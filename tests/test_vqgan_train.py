@@ -115,6 +115,29 @@ def test_training_reduces_the_loss_and_syncs_back():
     assert codes.shape == (x.shape[0], 16, 16)
 
 
+def test_global_norm_clip_scales_the_flat_gradient():
+    """gradient_clip_val at half the fp64 norm of the unclipped gradient: after apply_gradients() flat_g is the unclipped copy times
+    clip / (norm + 1e-6) (torch.nn.utils.clip_grad_norm_), within the clip kernel's own bound (tests/test_hip_training_kernels.py)"""
+    import training_kernels_ref as R
+    from oracle import vqgan_oracle as vq
+    from test_hip_training_kernels import C
+    g, cfg, sd = _tiny()
+    x = vq.preprocess_u8(torch.from_numpy(g['frames']))
+    tr = _trainer(cfg, sd)
+    tr.train_step(x, apply_update=False)
+    unclipped = tr.flat_g.cpu().clone()
+    norm = float(unclipped.double().norm())
+    assert np.isfinite(norm) and norm > 0
+    tr.cfg.gradient_clip_val = 0.5 * norm
+    tr.apply_gradients()
+    torch.cuda.synchronize()
+    want, mag = R.clip_grad_norm(unclipped, 0.5 * norm)
+    assert abs(float(want.norm()) / norm - 0.5) < 1e-6                          # the reference did clip
+    ratio = R.worst_ratio(tr.flat_g.cpu(), want, mag)
+    print('clipped flat_g: worst', ratio, 'x 2^-24 x |value|')
+    assert ratio <= C['clip_grad_norm_'], ratio
+
+
 @pytest.mark.parametrize('cfgkw,n', [
     (dict(ch=64, ch_mult=[1, 2], num_res_blocks=1, attn_resolutions=[16], image_size=32, z_channels=64, embed_dim=64, n_embed=128), 4),
     (dict(ch=128, ch_mult=[1, 1, 2], num_res_blocks=1, attn_resolutions=[16], image_size=64, z_channels=128, embed_dim=64, n_embed=128), 2),

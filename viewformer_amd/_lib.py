@@ -76,7 +76,7 @@ EXPORTS = {
     'vf_gather_transpose_f32': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, P]),
     'vf_upsample2_bwd_f32': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     'vf_groupnorm_bwd_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
-    'vf_groupnorm_bwd_f32': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'vf_groupnorm_bwd_f32': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P]),
     'vf_softmax_rows_bwd_f32': (c_int, [P, P, c_int64, c_int, c_float, P]),
     'vf_l1_loss_partials': (c_int, [c_int64]),
     'vf_l1_loss_f32': (c_int, [P, P, P, P, c_int64, c_float, P]),
@@ -178,6 +178,7 @@ EXPORTS = {
     'vf_adamw_flat_pack_f32': (c_int, [P, P, P, P, c_int64, P, c_int, c_float, c_float, c_float, c_float, c_float, P, c_int, P]),
     'vf_axpby_f32': (c_int, [c_float, P, c_float, P, P, c_int64, P]),
     'vf_add_inplace_f32': (c_int, [P, P, c_int64, P]),
+    'vf_clip_scratch_floats': (c_int, []),
     'vf_clip_by_norm_f32': (c_int, [P, c_int64, c_float, P, P]),
     'vf_clip_grad_norm_f32': (c_int, [P, c_int64, c_float, P, P]),
 }

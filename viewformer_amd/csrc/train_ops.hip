@@ -838,21 +838,44 @@ __global__ void axpby_kernel(float a, const float* __restrict__ x, float b, cons
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         out[i] = a * x[i] + (y ? b * y[i] : 0.f);
 }
-__global__ void sumsq_kernel(const float* __restrict__ x, float* __restrict__ out, long long n) {
+// Global sum of squares without a float atomic (the rule of the embedding backward below holds here too: the clip factor scales every
+// gradient, so its low bits must not depend on scheduling).  Block b of at most CLIP_MAX_PARTIALS writes part[b]: its threads' strided
+// sums folded by the fixed butterfly of vf_wave_sum, the four wave sums added in wave order.  Every block of the scaling kernel then
+// adds the partials in one fixed order of its own (clip_total), so all blocks hold the same bits and no further launch is needed.
+constexpr int CLIP_MAX_PARTIALS = 1024;
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, float* __restrict__ part, long long n) {
+    __shared__ float red[4];
     float s = 0.f;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) s += x[i] * x[i];
     s = vf_wave_sum(s);
-    if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
-__global__ void scale_kernel(float* __restrict__ x, const float* __restrict__ sumsq, float clip, long long n) {
+// thread t adds part[4 t .. 4 t + 3] in index order; the 256 sums are folded as in sumsq_kernel (256-thread blocks only)
+__device__ __forceinline__ float clip_total(const float* __restrict__ part, int nparts) {
+    __shared__ float red[4];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < CLIP_MAX_PARTIALS / 256; ++j) {
+        const int k = (int)threadIdx.x * (CLIP_MAX_PARTIALS / 256) + j;
+        if (k < nparts) s += part[k];
+    }
+    s = vf_wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, const float* __restrict__ part, int nparts, float clip, long long n) {
     // tf.clip_by_norm: x * clip / max(norm, clip)
-    const float norm = sqrtf(*sumsq);
+    const float norm = sqrtf(clip_total(part, nparts));
     const float f = clip / fmaxf(norm, clip);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) x[i] *= f;
 }
-__global__ void scale_gradnorm_kernel(float* __restrict__ x, const float* __restrict__ sumsq, float max_norm, long long n) {
+__global__ __launch_bounds__(256) void scale_gradnorm_kernel(float* __restrict__ x, const float* __restrict__ part, int nparts, float max_norm,
+                                                             long long n) {
     // torch.nn.utils.clip_grad_norm_: coef = max_norm / (total_norm + 1e-6); grads *= coef only when coef < 1
-    const float f = max_norm / (sqrtf(*sumsq) + 1e-6f);
+    const float f = max_norm / (sqrtf(clip_total(part, nparts)) + 1e-6f);
     if (!(f < 1.0f)) return;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) x[i] *= f;
 }
@@ -1223,23 +1246,24 @@ int vf_axpby_f32(float a, const float* x, float b, const float* y, float* out, i
     return vf_last_status();
 }
 
-int vf_clip_by_norm_f32(float* x, int64_t n, float clip, float* scratch1, void* stream) {
-    if (!x || !scratch1 || n <= 0 || clip <= 0.f) return VF_ERR_BAD_ARG;
+/* floats of scratch the two clip entry points need (the per-block partial sums of squares) */
+int vf_clip_scratch_floats(void) { return CLIP_MAX_PARTIALS; }
+
+int vf_clip_by_norm_f32(float* x, int64_t n, float clip, float* scratch, void* stream) {
+    if (!x || !scratch || n <= 0 || clip <= 0.f) return VF_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(scratch1, 0, sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(grid1(n, 256, 1024)), dim3(256), 0, s, x, scratch1, (long long)n);
-    hipLaunchKernelGGL(scale_kernel, dim3(grid1(n, 256, 8192)), dim3(256), 0, s, x, scratch1, clip, (long long)n);
+    const unsigned nparts = grid1(n, 256, CLIP_MAX_PARTIALS);
+    hipLaunchKernelGGL(sumsq_kernel, dim3(nparts), dim3(256), 0, s, x, scratch, (long long)n);
+    hipLaunchKernelGGL(scale_kernel, dim3(grid1(n, 256, 8192)), dim3(256), 0, s, x, scratch, (int)nparts, clip, (long long)n);
     return vf_last_status();
 }
 
-int vf_clip_grad_norm_f32(float* x, int64_t n, float max_norm, float* scratch1, void* stream) {
-    if (!x || !scratch1 || n <= 0 || !(max_norm > 0.f)) return VF_ERR_BAD_ARG;
+int vf_clip_grad_norm_f32(float* x, int64_t n, float max_norm, float* scratch, void* stream) {
+    if (!x || !scratch || n <= 0 || !(max_norm > 0.f)) return VF_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(scratch1, 0, sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(grid1(n, 256, 1024)), dim3(256), 0, s, x, scratch1, (long long)n);
-    hipLaunchKernelGGL(scale_gradnorm_kernel, dim3(grid1(n, 256, 8192)), dim3(256), 0, s, x, scratch1, max_norm, (long long)n);
+    const unsigned nparts = grid1(n, 256, CLIP_MAX_PARTIALS);
+    hipLaunchKernelGGL(sumsq_kernel, dim3(nparts), dim3(256), 0, s, x, scratch, (long long)n);
+    hipLaunchKernelGGL(scale_gradnorm_kernel, dim3(grid1(n, 256, 8192)), dim3(256), 0, s, x, scratch, (int)nparts, max_norm, (long long)n);
     return vf_last_status();
 }
 

@@ -59,68 +59,90 @@ __global__ void sum2x2_kernel(const float* __restrict__ du, float* __restrict__ 
 // GroupNorm(+swish) backward.  Forward: xhat = (x - mean) * rstd, t = xhat * gamma + beta, a = swish ? t * sigmoid(t) : t.
 // Given da: dt = da * da/dt;  dgamma[c] = sum dt * xhat, dbeta[c] = sum dt;  per (image, group) m1 = mean(gamma dt),
 // m2 = mean(gamma dt xhat);  dx = rstd * (gamma dt - m1 - xhat m2).   mean_c / scale_c are the forward's [Nimg][C] (scale = rstd*gamma).
+// rstd is a property of the (image, group), not of a channel, and is never obtained by dividing by the channel's own gain (a zero or
+// denormal gain made that 0/0 and the NaN spread over the whole group through m1 / m2): t = (x - mean) * scale + beta as the forward
+// computed it, the channel sums are taken over (x - mean), and stage 2 recovers one rstd per group from the channel of largest |scale|
+// — or, where every gain of the group is (almost) zero, from the group's own sum of (x - mean)^2, which stage 1 collects in the pass
+// it makes anyway.
 __device__ __forceinline__ float dswish(float t) {
     const float s = 1.0f / (1.0f + expf(-t));
     return s * (1.0f + t * (1.0f - s));
 }
 
-// stage 1: grid (nsplit, n_img), per-channel partial sums over the split's pixels: part[img][split][C][2] = {sum dt, sum dt*xhat}
+constexpr float GN_SCALE_MIN = 0x1p-100f;     // below this |rstd * gamma| the quotient scale / gamma no longer carries rstd's 24 bits
+
+// stage 1: grid (nsplit, n_img), per-channel partial sums over the split's pixels:
+// part[img][split][C][3] = {sum dt, sum dt*(x - mean), sum (x - mean)^2}
 __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ da,
                                                              const float* __restrict__ mean_c, const float* __restrict__ scale_c,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             float* __restrict__ part, int HW, int C, int nsplit, int swish) {
+                                                             const float* __restrict__ beta, float* __restrict__ part, int HW, int C,
+                                                             int nsplit, int swish) {
     const int img = blockIdx.y, split = blockIdx.x;
     const int per = (HW + nsplit - 1) / nsplit;
     const int p0 = split * per, p1 = min(HW, p0 + per);
     for (int c = threadIdx.x; c < C; c += 256) {
-        const float mu = mean_c[(size_t)img * C + c], sg = scale_c[(size_t)img * C + c], g = gamma[c], b = beta[c];
-        const float rstd = sg / g;
-        float s1 = 0.f, s2 = 0.f;
+        const float mu = mean_c[(size_t)img * C + c], sg = scale_c[(size_t)img * C + c], b = beta[c];
+        float s1 = 0.f, s2 = 0.f, s3 = 0.f;
         for (int p = p0; p < p1; ++p) {
             const size_t i = ((size_t)img * HW + p) * C + c;
-            const float xh = (x[i] - mu) * rstd;
+            const float xc = x[i] - mu;
             float dt = da[i];
-            if (swish) dt *= dswish(xh * g + b);
+            if (swish) dt *= dswish(xc * sg + b);
             s1 += dt;
-            s2 += dt * xh;
+            s2 += dt * xc;
+            s3 += xc * xc;
         }
-        float* d = part + ((((size_t)img * nsplit + split) * C) + c) * 2;
+        float* d = part + ((((size_t)img * nsplit + split) * C) + c) * 3;
         d[0] = s1;
         d[1] = s2;
+        d[2] = s3;
     }
 }
 
-// stage 2: one block per image: reduce the splits (fixed order), per-group means -> gm[img][groups][2]; per-image channel sums
-// -> chan[img][C][2] (dgamma / dbeta contributions, summed over images by the caller's column sum)
-__global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
-                                                            float* __restrict__ chan, float* __restrict__ gm, int HW, int C,
-                                                            int groups, int nsplit) {
-    __shared__ float s1s[1024], s2s[1024];
+// stage 2: one block per image: reduce the splits (fixed order), per-group rstd and means -> gm[img][groups][3] = {m1, m2, rstd};
+// per-image channel sums -> chan[img][C][2] (dgamma / dbeta contributions, summed over images by the caller's column sum)
+__global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float* __restrict__ part, const float* __restrict__ scale_c,
+                                                            const float* __restrict__ gamma, float* __restrict__ chan,
+                                                            float* __restrict__ gm, int HW, int C, int groups, int nsplit, float eps) {
+    __shared__ float s1s[1024], s2s[1024], s3s[1024], rs[1024];
     const int img = blockIdx.x;
     for (int c = threadIdx.x; c < C; c += 256) {
-        float a = 0.f, b = 0.f;
+        float a = 0.f, b = 0.f, q = 0.f;
         for (int s = 0; s < nsplit; ++s) {
-            const float* d = part + ((((size_t)img * nsplit + s) * C) + c) * 2;
+            const float* d = part + ((((size_t)img * nsplit + s) * C) + c) * 3;
             a += d[0];
             b += d[1];
+            q += d[2];
         }
         s1s[c] = a;
         s2s[c] = b;
-        chan[((size_t)img * C + c) * 2] = b;          // dgamma contribution
-        chan[((size_t)img * C + c) * 2 + 1] = a;      // dbeta contribution
+        s3s[c] = q;
     }
     __syncthreads();
     const int cg = C / groups;
     for (int g = threadIdx.x; g < groups; g += 256) {
-        float m1 = 0.f, m2 = 0.f;
+        float m1 = 0.f, m2 = 0.f, sq = 0.f, best = 0.f;
+        int cb = g * cg;
         for (int k = 0; k < cg; ++k) {
             const int c = g * cg + k;
             m1 += gamma[c] * s1s[c];
             m2 += gamma[c] * s2s[c];
+            sq += s3s[c];
+            const float sa = fabsf(scale_c[(size_t)img * C + c]);
+            if (sa > best) { best = sa; cb = c; }
         }
         const float inv = 1.0f / ((float)HW * cg);
-        gm[((size_t)img * groups + g) * 2] = m1 * inv;
-        gm[((size_t)img * groups + g) * 2 + 1] = m2 * inv;
+        const float rstd = best >= GN_SCALE_MIN ? scale_c[(size_t)img * C + cb] / gamma[cb] : 1.0f / sqrtf(sq * inv + eps);
+        rs[g] = rstd;
+        float* o = gm + ((size_t)img * groups + g) * 3;
+        o[0] = m1 * inv;
+        o[1] = rstd * (m2 * inv);
+        o[2] = rstd;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        chan[((size_t)img * C + c) * 2] = rs[c / cg] * s2s[c];      // dgamma contribution
+        chan[((size_t)img * C + c) * 2 + 1] = s1s[c];              // dbeta contribution
     }
 }
 
@@ -133,13 +155,12 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, const float* __
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(i % C);
         const long long img = i / ((long long)HW * C);
-        const float mu = mean_c[img * C + c], sg = scale_c[img * C + c], g = gamma[c];
-        const float rstd = sg / g;
-        const float xh = (x[i] - mu) * rstd;
+        const float xc = x[i] - mean_c[img * C + c];
         float dt = da[i];
-        if (swish) dt *= dswish(xh * g + beta[c]);
-        const float* m = gm + (img * groups + c / cg) * 2;
-        const float v = rstd * (g * dt - m[0] - xh * m[1]);
+        if (swish) dt *= dswish(xc * scale_c[img * C + c] + beta[c]);
+        const float* m = gm + (img * groups + c / cg) * 3;
+        const float rstd = m[2];
+        const float v = rstd * (gamma[c] * dt - m[0] - (xc * rstd) * m[1]);
         dx[i] = accumulate ? dx[i] + v : v;
     }
 }
@@ -211,25 +232,27 @@ size_t vf_groupnorm_bwd_workspace_bytes(int n_img, int HW, int C, int groups) {
     int nsplit = HW / 64;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > 64) nsplit = 64;
-    return ((size_t)n_img * nsplit * C * 2 + (size_t)n_img * C * 2 + (size_t)n_img * groups * 2) * sizeof(float);
+    return ((size_t)n_img * nsplit * C * 3 + (size_t)n_img * groups * 3) * sizeof(float);
 }
 
-/* chan_sums out: [n_img][C][2] = per-image {dgamma, dbeta} contributions (the caller sums over images) */
+/* chan_sums out: [n_img][C][2] = per-image {dgamma, dbeta} contributions (the caller sums over images); eps = the forward's
+ * (vf_groupnorm_stats_f32): read only for a group whose gains are all zero, where scale_c no longer holds its rstd */
 int vf_groupnorm_bwd_f32(const float* x, const float* da, const float* mean_c, const float* scale_c, const float* gamma,
-                         const float* beta, float* dx, float* chan_sums, int n_img, int HW, int C, int groups, int swish,
+                         const float* beta, float* dx, float* chan_sums, int n_img, int HW, int C, int groups, float eps, int swish,
                          int accumulate, void* ws, void* stream) {
     if (!x || !da || !mean_c || !scale_c || !gamma || !beta || !dx || !chan_sums || !ws) return VF_ERR_BAD_ARG;
+    if (!(eps >= 0.f)) return VF_ERR_BAD_ARG;
     if (n_img <= 0 || HW <= 0 || C <= 0 || groups <= 0 || C % groups != 0 || C > 1024) return VF_ERR_UNSUPPORTED;
     int nsplit = HW / 64;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > 64) nsplit = 64;
     float* part = (float*)ws;
-    float* gm = part + (size_t)n_img * nsplit * C * 2;
+    float* gm = part + (size_t)n_img * nsplit * C * 3;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nsplit, n_img), dim3(256), 0, s, x, da, mean_c, scale_c, gamma, beta, part, HW, C,
-                       nsplit, swish);
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(n_img), dim3(256), 0, s, (const float*)part, gamma, chan_sums, gm, HW, C, groups,
-                       nsplit);
+    hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nsplit, n_img), dim3(256), 0, s, x, da, mean_c, scale_c, beta, part, HW, C, nsplit,
+                       swish);
+    hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(n_img), dim3(256), 0, s, (const float*)part, scale_c, gamma, chan_sums, gm, HW,
+                       C, groups, nsplit, eps);
     const long long total = (long long)n_img * HW * C;
     hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid1(total, 256)), dim3(256), 0, s, x, da, mean_c, scale_c, gamma, beta,
                        (const float*)gm, dx, total, HW, C, groups, swish, accumulate);

@@ -296,7 +296,7 @@ class MIGTTrainer:
         self.flat_g = torch.zeros_like(self.flat_p)
         self.flat_m = torch.zeros_like(self.flat_p)
         self.flat_v = torch.zeros_like(self.flat_p)
-        self._scratch = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._scratch = None                                   # clip scratch (T.clip_scratch), allocated by the first clipped step
 
     def p(self, name):
         a, b, s = self.slices[name]
@@ -1031,6 +1031,8 @@ class MIGTTrainer:
         self._flush_unset()
         self._join_side()
         if c.gradient_clip_val and c.gradient_clip_val > 0:
+            if self._scratch is None:
+                self._scratch = T.clip_scratch(self.flat_g.device)
             for n in self.names:
                 T.clip_by_norm_(self.g(n).reshape(-1), float(c.gradient_clip_val), self._scratch)
         if reduce_gradients and self._world() > 1:

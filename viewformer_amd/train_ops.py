@@ -225,14 +225,25 @@ def axpby(a, x, b=0.0, y=None, out=None):
     return out
 
 
-def clip_by_norm_(x, clip, scratch1):
-    check(_lib.load().vf_clip_by_norm_f32(_p(_f32(x)), x.numel(), clip, _p(scratch1), _stream()), 'vf_clip_by_norm_f32')
+def clip_scratch(device):
+    """the scratch buffer of clip_by_norm_ / clip_grad_norm_ (vf_clip_scratch_floats() floats; needs no initialisation)"""
+    return torch.empty(int(_lib.load().vf_clip_scratch_floats()), dtype=torch.float32, device=device)
+
+
+def _clip_scratch_ok(scratch):
+    if _f32(scratch).numel() < int(_lib.load().vf_clip_scratch_floats()):
+        raise _lib.VfError('clip: scratch holds fewer than vf_clip_scratch_floats() floats (train_ops.clip_scratch allocates it)')
+    return scratch
+
+
+def clip_by_norm_(x, clip, scratch):
+    check(_lib.load().vf_clip_by_norm_f32(_p(_f32(x)), x.numel(), clip, _p(_clip_scratch_ok(scratch)), _stream()), 'vf_clip_by_norm_f32')
     return x
 
 
-def clip_grad_norm_(x, max_norm, scratch1):
+def clip_grad_norm_(x, max_norm, scratch):
     """global-norm clip of a flat gradient buffer (torch.nn.utils.clip_grad_norm_ semantics)"""
-    check(_lib.load().vf_clip_grad_norm_f32(_p(_f32(x)), x.numel(), max_norm, _p(scratch1), _stream()), 'vf_clip_grad_norm_f32')
+    check(_lib.load().vf_clip_grad_norm_f32(_p(_f32(x)), x.numel(), max_norm, _p(_clip_scratch_ok(scratch)), _stream()), 'vf_clip_grad_norm_f32')
     return x
 
 
@@ -334,14 +345,15 @@ def upsample2_bwd(du, n_img, H, W, C):
     return dx
 
 
-def groupnorm_bwd(x, da, mean_c, scale_c, gamma, beta, n_img, HW, C, swish, groups=32):
-    """-> (dx, dgamma [C], dbeta [C]) of a = swish?(GroupNorm(x))"""
+def groupnorm_bwd(x, da, mean_c, scale_c, gamma, beta, n_img, HW, C, swish, groups=32, eps=1e-6):
+    """-> (dx, dgamma [C], dbeta [C]) of a = swish?(GroupNorm(x)); ``mean_c`` / ``scale_c`` / ``eps``: the forward's (ops.groupnorm_stats).
+    Zero and denormal gains are fine (csrc/vqgan_bwd.hip)"""
     lib = _lib.load()
     dx = torch.empty_like(x)
     chan = torch.empty((n_img, C, 2), dtype=torch.float32, device=x.device)
     ws = _ws(int(lib.vf_groupnorm_bwd_workspace_bytes(n_img, HW, C, groups)), x.device, 'gnbwd')
     check(lib.vf_groupnorm_bwd_f32(_p(_f32(x)), _p(_f32(da)), _p(mean_c), _p(scale_c), _p(_f32(gamma)), _p(_f32(beta)), _p(dx),
-                                   _p(chan), n_img, HW, C, groups, 1 if swish else 0, 0, _p(ws), _stream()), 'vf_groupnorm_bwd_f32')
+                                   _p(chan), n_img, HW, C, groups, float(eps), 1 if swish else 0, 0, _p(ws), _stream()), 'vf_groupnorm_bwd_f32')
     sums = torch.empty(2 * C, dtype=torch.float32, device=x.device)
     colsum(chan.view(n_img, 2 * C), sums, n_img, 2 * C)
     sums = sums.view(C, 2)
