@@ -357,6 +357,22 @@ int vf_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n_img, int H, in
 size_t vf_camera_knn_workspace_bytes(int64_t N, int Q, int k);
 int vf_camera_knn_f32(const float* db, int64_t N, const float* queries, int Q, int k, float pos_weight, int32_t* idx, float* dist,
                       void* workspace, void* stream);
+/* the tail of the localization head in one launch (csrc/pose_tail.hip; host: ops.pose_tail, MIGT.localize_from_context): the pose
+ * classifier's c_proj, MLP(n_state, 7) viewformer/models/migt.py:291-292,354, QuaternionPoseRepresentation's output branch :159-164 and
+ * its reduce :123-129,150-154.  x [views * L][K] fp32 with row stride ldx (the GELU output of c_fc), W [K][7] as stored (x @ W + b),
+ * b [7] or NULL.
+ *   raw     [views * L][7] = x @ W + b                                                                     (may be NULL)
+ *   tokens  [views * L][7]: xyz = raw.xyz / position_multiplier (IEEE division); q = raw.q / sqrt(max(sum raw.q^2, 1e-12)), multiplied
+ *                           by (q.w >= 0 ? 1 : -1)                                                         (may be NULL)
+ *   cameras [views][7]:     xyz = mean of the view's L token xyz; q = the mean of its tokens' q, normalised and sign-fixed the same way
+ * fp32; one workgroup per view, sums in a fixed order, no atomics: a view's outputs are bit-identical whatever `views` is, wherever the
+ * view sits, and whichever optional outputs are requested.  Footprint: reads the K logical floats of each of the views * L rows of x (not
+ * the ldx - K gap), K * 7 floats of W and 7 of b; writes exactly views * L * 7 floats of raw and of tokens where given and views * 7 of
+ * cameras, all dense; no workspace.  NULL x / W / cameras, x not 16-byte aligned, views < 0, K <= 0, ldx < K or a position_multiplier that
+ * is zero or not finite: VF_ERR_BAD_ARG.  Supported: K % 4 == 0, 4 <= K <= 2048, 1 <= L <= 256, ldx % 4 == 0, views < 2^31; anything else
+ * is VF_ERR_UNSUPPORTED; both before any launch.  views == 0 is a no-op. */
+int vf_pose_tail_f32(const float* x, int64_t ldx, const float* W, const float* b, float position_multiplier, int64_t views, int L, int K,
+                     float* raw, float* tokens, float* cameras, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Reduced-precision arm (bf16 MFMA, fp32 activations in HBM, fp32 accumulate / epilogue) for the layers whose

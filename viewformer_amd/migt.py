@@ -329,6 +329,32 @@ class MIGT:
         self._blocks(codes, self._pose_embed(cameras), B, C, L, kv_sink=kv)
         return ContextCache(self, kv, B, C, tshape)
 
+    def _query_rows(self, cache, ids32, add, N):
+        """The per-layer loop over the rows of N query views per scene of ``cache``: ``ids32`` int32 [B*N*L] token ids, ``add`` fp32
+        [B*N, d] (a pose embedding or the LOC row per view) -> ln_f hidden states [B*N*L, d].  Each view attends to the cached context
+        and to itself (ops.attn_prefix); its rows go through the LayerNorm / dense launches of the full pass."""
+        c, dev = self.config, self.device
+        B, C = cache.B, cache.C
+        L = int(np.prod(cache.tshape))
+        d, H, nE = c.d_model, c.n_head, c.n_embeddings
+        M = B * N * L
+        h = ops.embed_sum(ids32, self._wte, self._wpe, add, B * N, L, d, nE + 2)           # migt.py:392
+        act16, qkv16 = cache.act16, cache.qkv16
+        att = torch.empty((M, d), dtype=torch.bfloat16 if act16 else torch.float32, device=dev)
+        qkv = torch.empty((M, 3 * d), dtype=torch.bfloat16 if qkv16 else torch.float32, device=dev)
+        for i in range(c.n_layer):                                           # Block.call on the query rows, migt.py:230-238
+            p = f'h.{i}'
+            a = ops.layernorm(h, *self._ln[p + '.ln_1'], M, d, out_bf16=act16)
+            self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
+            ckv = cache.kv[i]                                                # [B*C*L, 3d], thirds (V, Q, K)
+            ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
+                            3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16')
+            h = self._gemm(att, p + '.attn.c_proj', M, res=h)
+            m = ops.layernorm(h, *self._ln[p + '.ln_2'], M, d, out_bf16=act16)
+            f = self._gemm(m, p + '.mlp.c_fc', M, epilogue=ops.EPI_GELU, out_bf16=act16)
+            h = self._gemm(f, p + '.mlp.c_proj', M, res=h)
+        return ops.layernorm(h, *self._ln['ln_f'], M, d)                     # migt.py:408
+
     def generate_from_context(self, cache, query_cameras, codes_only: bool = True):
         """N novel views per scene from a prefilled context: ``query_cameras`` fp32 [B,N,7] in the context's (relative, normalised)
         frame -> generated code maps int64 [B,N,t,t], or with ``codes_only=False`` the logits [B,N,t,t,n_embeddings].  Every query is
@@ -353,22 +379,7 @@ class MIGT:
                     else torch.empty((B, 0, *tshape, nE), dtype=torch.float32, device=dev))
         add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
         ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
-        h = ops.embed_sum(ids32, self._wte, self._wpe, add, B * N, L, d, nE + 2)           # migt.py:392
-        act16, qkv16 = cache.act16, cache.qkv16
-        att = torch.empty((M, d), dtype=torch.bfloat16 if act16 else torch.float32, device=dev)
-        qkv = torch.empty((M, 3 * d), dtype=torch.bfloat16 if qkv16 else torch.float32, device=dev)
-        for i in range(c.n_layer):                                           # Block.call on the query rows, migt.py:230-238
-            p = f'h.{i}'
-            a = ops.layernorm(h, *self._ln[p + '.ln_1'], M, d, out_bf16=act16)
-            self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
-            ckv = cache.kv[i]                                                # [B*C*L, 3d], thirds (V, Q, K)
-            ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
-                            3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16')
-            h = self._gemm(att, p + '.attn.c_proj', M, res=h)
-            m = ops.layernorm(h, *self._ln[p + '.ln_2'], M, d, out_bf16=act16)
-            f = self._gemm(m, p + '.mlp.c_fc', M, epilogue=ops.EPI_GELU, out_bf16=act16)
-            h = self._gemm(f, p + '.mlp.c_proj', M, res=h)
-        hf = ops.layernorm(h, *self._ln['ln_f'], M, d)                       # migt.py:408
+        hf = self._query_rows(cache, ids32, add, N)
         gen = self._lm_argmax(hf, M) if codes_only else None
         if gen is None:
             lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
@@ -377,6 +388,54 @@ class MIGT:
                 return lg.view(B, N, *tshape, nE)
             gen = ops.argmax_rows(lg, M, nE)
         return gen.view(B, N, *tshape)
+
+    def localize_from_context(self, cache, codes, return_tokens: bool = False, fused_tail: bool = True):
+        """Localize N photos per scene against a prefilled context: ``codes`` int [B,N,t,t] (the photos' code maps) -> cameras fp32
+        [B,N,7] in the context's (relative, normalised) frame; with ``return_tokens`` a dict(cameras, pose_prediction [B,N,L,7],
+        raw [B,N,L,7] — the pose classifier's output before post-processing).  Every photo is a LOC view — ``wte[codes] + wpe +
+        wte[LOC]``, no pose: the last view of ``model(dict(input_ids=[ctx, photo], poses=ctx_poses))`` — that sees the context and itself,
+        which is ``generate_from_context``'s visibility: the same loop over its rows (``_query_rows``), no LM head, then the pose
+        classifier.  ``fused_tail``: c_proj, the per-token post-processing and the reduction over a view's tokens as one launch
+        (ops.pose_tail) where the kernel takes the shape; otherwise, and with ``fused_tail=False``, the GEMM and
+        geometry.pose_head_postprocess / reduce_cameras as ``__call__`` and the evaluators run them.  Photos are independent of each
+        other: a photo's result does not depend on N."""
+        if not self.use_localization:
+            raise RuntimeError('localize_from_context needs a model with the localization head')
+        if not isinstance(cache, ContextCache):
+            raise TypeError('localize_from_context: a ContextCache from prefill_context expected')
+        B, tshape = cache.B, cache.tshape
+        L = int(np.prod(tshape))
+        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
+        cache.check(self)
+        c, dev = self.config, self.device
+        codes = torch.as_tensor(codes).to(dev)
+        if codes.dim() != 2 + len(tshape) or codes.shape[0] != B or tuple(codes.shape[2:]) != tshape or codes.dtype.is_floating_point:
+            raise ValueError(f'codes int [B={B},N,{",".join(map(str, tshape))}] expected for this cache, got {codes.dtype} {tuple(codes.shape)}')
+        N = codes.shape[1]
+        d = c.d_model
+        M = B * N * L
+        if N == 0:
+            cams = torch.empty((B, 0, 7), dtype=torch.float32, device=dev)
+            if not return_tokens:
+                return cams
+            return dict(cameras=cams, pose_prediction=torch.empty((B, 0, L, 7), dtype=torch.float32, device=dev),
+                        raw=torch.empty((B, 0, L, 7), dtype=torch.float32, device=dev))
+        add = self._wte[self.localization_token].view(1, d).expand(B * N, d).contiguous()            # migt.py:387-390
+        ids32 = codes.reshape(M).to(torch.int32).contiguous()
+        hf = self._query_rows(cache, ids32, add, N)
+        p1 = self._gemm(hf, 'pose_criterion.pose_classifier.c_fc', M, epilogue=ops.EPI_GELU)
+        cp = self._dense['pose_criterion.pose_classifier.c_proj']
+        if fused_tail and cp.n == 7 and ops.pose_tail_supported(cp.k, L):
+            cams, tokens, raw = ops.pose_tail(p1, cp.w_raw, cp.bias, c.pose_multiplier, B * N, L, want_raw=return_tokens,
+                                              want_tokens=return_tokens)
+        else:
+            raw = self._gemm(p1, 'pose_criterion.pose_classifier.c_proj', M).view(B * N, L, 7)
+            tokens = geometry.pose_head_postprocess(raw, c.pose_multiplier)
+            cams = geometry.reduce_cameras(tokens, -2)
+        cams = cams.view(B, N, 7)
+        if not return_tokens:
+            return cams
+        return dict(cameras=cams, pose_prediction=tokens.view(B, N, L, 7), raw=raw.view(B, N, L, 7))
 
     def generate_and_localize(self, codes, cameras, codes_only: bool = False):
         """The evaluator's two transformer passes (evaluate_transformer.py:119-123 and :134-136) as ONE pass.

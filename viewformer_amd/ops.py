@@ -740,3 +740,30 @@ def camera_knn(db, queries, k, pos_weight=0.3, return_dist=False):
     ws = torch.empty(max(int(lib.vf_camera_knn_workspace_bytes(N, Q, k)), 8), dtype=torch.uint8, device=db.device)
     check(lib.vf_camera_knn_f32(_p(db), N, _p(queries), Q, k, float(pos_weight), _p(idx), _p(dist), _p(ws), _stream()), 'vf_camera_knn_f32')
     return (idx, dist) if return_dist else idx
+
+
+def pose_tail_supported(K, L):
+    """shapes vf_pose_tail_f32 takes: K features per row (a multiple of 4, at most 2048), L tokens per view (at most 256)"""
+    return K % 4 == 0 and 4 <= K <= 2048 and 1 <= L <= 256
+
+
+def pose_tail(x, W, b, position_multiplier, views, L, want_raw=False, want_tokens=False):
+    """The localization head's tail in one launch (vf_pose_tail_f32): x [views*L, K] fp32 rows (row stride a multiple of 4; the GELU
+    output of pose_classifier.c_fc), W [K,7] as stored, b [7] or None -> (cameras [views,7], tokens [views,L,7] | None,
+    raw [views,L,7] | None): raw = x @ W + b, tokens = geometry.pose_head_postprocess(raw, position_multiplier), cameras =
+    geometry.reduce_cameras(tokens, -2).  A view's outputs do not depend on the other views of the call or on the optional outputs."""
+    if x.dim() != 2 or x.shape[0] != views * L or x.stride(1) != 1 or W.dim() != 2 or tuple(W.shape) != (x.shape[1], 7):
+        raise ValueError(f'pose_tail: x [views*L = {views * L}, K] with unit column stride and W [K,7] expected, got {tuple(x.shape)} '
+                         f'(strides {tuple(x.stride())}) and {tuple(W.shape)}')
+    if b is not None and b.numel() != 7:
+        raise ValueError(f'pose_tail: b [7] expected, got {tuple(b.shape)}')
+    K = x.shape[1]
+    W = _f32(W, 'W').contiguous()
+    b = _f32(b, 'b').contiguous() if b is not None else None
+    dev = x.device
+    cameras = torch.empty((views, 7), dtype=torch.float32, device=dev)
+    tokens = torch.empty((views, L, 7), dtype=torch.float32, device=dev) if want_tokens else None
+    raw = torch.empty((views, L, 7), dtype=torch.float32, device=dev) if want_raw else None
+    check(_lib.load().vf_pose_tail_f32(_p(_f32(x, 'x')), x.stride(0) if views * L > 1 else max(x.stride(0), K), _p(W), _p(b),
+                                       float(position_multiplier), views, L, K, _p(raw), _p(tokens), _p(cameras), _stream()), 'vf_pose_tail_f32')
+    return cameras, tokens, raw

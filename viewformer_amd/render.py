@@ -1,4 +1,4 @@
-"""Novel-view rendering: many query views from ONE context, without target frames.
+"""Many query views from ONE context: novel-view rendering without target frames, and localization of photos.
 
 ``evaluate.generate_batch_predictions`` is the evaluator's loop body: S views in, one view out, and it wants an image for the view it is
 about to generate.  An orbit of N views around C photographs costs it N * (C + 1) encoder passes and N * (C + 1) transformer views.  The
@@ -9,12 +9,18 @@ and values are computed once (``MIGT.prefill_context``) and each query is a sing
     r = ViewRenderer(transformer_model, codebook_model)
     r.set_context(images=frames_u8, cameras=cams)            # or codes=... (scene_bank.SceneBank.gather)
     out = r.render(query_cameras)                            # out['generated_images'] uint8 [B,N,H,W,3]
+    est = r.localize(images=photos_u8)                       # est['generated_cameras'] fp32 [B,N,7], the caller's world frame
 
 Contract: ``render(q)['generated_images'][b, n]`` is what ``generate_batch_predictions`` generates for the scene (context views of b...,
-any frame) with cameras (context cameras of b..., q[b, n]).
+any frame) with cameras (context cameras of b..., q[b, n]); ``localize(photos)['generated_cameras'][b, n]`` is what it returns as
+``generated_cameras`` for the scene (context views of b..., photos[b, n]) with cameras (context cameras of b..., anything).
 
-Not covered here: localization from the cache (the LOC view needs the target's codes) and the multi-context ``evaluate_sequence``
-path; both keep their evaluators.
+Localization uses the same cache: the LOC view of a photo is ``wte[codes] + wpe + wte[LOC]`` — no pose — and sees the
+context and itself, so N photos against C context photographs cost N encodes and N transformer views
+(``MIGT.localize_from_context``) instead of N * (C + 1) of each; one ``set_context`` serves ``render`` and ``localize`` alike.
+
+Not covered here: contexts that change per query (the 7-Scenes pose-refinement loop) and the multi-context ``evaluate_sequence`` path;
+both keep their evaluators.
 """
 import torch
 
@@ -66,6 +72,7 @@ class ViewRenderer:
         self.cache = None
         self.transform = None
         self.context_codes = None
+        self.fused_tail = None             # localize: None = MIGT.localize_from_context's default tail, True / False = the fused / unfused one
 
     def set_context(self, images=None, cameras=None, codes=None):
         """``images`` uint8 [B,C,H,W,3] (host or device; resized for the encoder as the evaluators do) or ``codes`` int [B,C,t,t]
@@ -144,9 +151,59 @@ class ViewRenderer:
                        decoded=dec.view(B, N, *dec.shape[1:]))
         return res
 
+    def localize(self, images=None, codes=None, max_views_per_call: int = None, return_tokens: bool = False):
+        """Estimate the cameras of N photos per scene against the context: ``images`` uint8 [B,N,H,W,3] (host or device; resized for
+        the encoder as the evaluators do, each photo encoded once) or ``codes`` int [B,N,t,t] (already encoded, e.g.
+        ``SceneBank.gather``) -> dict(generated_cameras fp32 [B,N,7]) in the caller's world frame (the context cameras'); with
+        ``return_tokens`` also codes int32 [B,N,t,t], pose_prediction [B,N,L,7] (the per-token poses in the context's frame) and raw
+        [B,N,L,7].  N is walked in chunks of whole views (``plan_view_chunks``)."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.localize: set_context() first')
+        if (images is None) == (codes is None):
+            raise ValueError('localize: exactly one of images / codes expected')
+        tm, cm = self.transformer, self.codebook
+        dev = cm.device
+        B = self.cache.B
+        t = tm.config.token_image_size
+        if codes is None:
+            images = torch.as_tensor(images).to(dev)
+            if images.dim() != 5 or images.shape[0] != B:
+                raise ValueError(f'localize: images [B={B},N,H,W,3] expected, got {tuple(images.shape)}')
+            N = images.shape[1]
+            if N:
+                codes = cm.encode(_frames_for_encode(images, cm.config.image_size))[-1]
+            else:
+                codes = torch.empty((B, 0, t, t), dtype=torch.int32, device=dev)
+        else:
+            codes = torch.as_tensor(codes).to(dev)
+            if codes.dim() < 2 or codes.shape[0] != B or codes.numel() % (B * t * t) or codes.dtype.is_floating_point:
+                raise ValueError(f'localize: codes int [B={B},N,{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
+            N = codes.numel() // (B * t * t)
+        codes = codes.to(torch.int32).view(B, N, t, t)
+        kw = dict(return_tokens=return_tokens, **({} if self.fused_tail is None else dict(fused_tail=bool(self.fused_tail))))
+        parts = [tm.localize_from_context(self.cache, codes[:, a:b], **kw) for a, b in plan_view_chunks(N, B, max_views_per_call)]
+        if not parts:
+            parts = [tm.localize_from_context(self.cache, codes, **kw)]             # N = 0: empty tensors of the right shapes
+        cat = lambda ts: torch.cat(ts, 1) if len(ts) > 1 else ts[0]
+        cams = cat([p['cameras'] if return_tokens else p for p in parts])
+        if self.transform is not None:                                   # evaluate_transformer.py:139-140
+            cams = geometry.from_relative_cameras(cams, self.transform)
+        res = dict(generated_cameras=cams)
+        if return_tokens:
+            res.update(codes=codes, pose_prediction=cat([p['pose_prediction'] for p in parts]), raw=cat([p['raw'] for p in parts]))
+        return res
+
 
 def render_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.render``'s
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``max_views_per_call``, ``return_codes``."""
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
     return r.render(query_cameras, **kw)
+
+
+def localize_views(transformer_model, codebook_model, images, cameras, photos=None, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``photos`` uint8 [B,N,H,W,3] -> ``ViewRenderer.localize``'s
+    dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``photo_codes`` (the photos' codes instead of
+    ``photos``), ``max_views_per_call``, ``return_tokens``."""
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    return r.localize(images=photos, codes=kw.pop('photo_codes', None), **kw)
