@@ -105,6 +105,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                                                             float* __restrict__ dgb_part, long long rows, int d, float eps,
                                                             int rows_per_block, const float* __restrict__ res, __bf16* __restrict__ dx16,
                                                             uint32_t drop_thresh, float drop_scale, uint32_t drop_key, long long drop_row0) {
+    // Contraction is spelled out (the fused multiply-adds are __builtin_fmaf, everything else rounds operation by operation): left to the
+    // compiler, the one-row and the two-row instantiation fused different products of the sums of g and g xhat (ISA of <2, 2> against
+    // <2, 1>: the product g = dy gamma contracted into the sum of g, g xhat into its sum, in one float4 slot of one form only), so the two
+    // forms that vf_select(VF_SEL_LN_BWD_TWO_ROWS) chooses between differed in the last bits of dx for 256 < d <= 512
+#pragma clang fp contract(off)
     // each wave walks rows_per_block/4 rows and keeps per-lane dgamma/dbeta partials in registers
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nv = d >> 2;
@@ -172,9 +177,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                         gv[q][i][e] = g;
                         xv[q][i][e] = xh;
                         sg[q] += g;
-                        sgx[q] += g * xh;
+                        sgx[q] += g * xh;                           // (product and sum round separately: contraction is off)
                         if (live[q]) {
-                            dg[i][e] += dyv[q][i][e] * xh;
+                            dg[i][e] = __builtin_fmaf(dyv[q][i][e], xh, dg[i][e]);
                             db[i][e] += dyv[q][i][e];
                         }
                     }
@@ -195,7 +200,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                 if (c < nv) {
                     f32x4 o;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = rstd[q] * (gv[q][i][e] - sg[q] - xv[q][i][e] * sgx[q]);
+                    for (int e = 0; e < 4; ++e) o[e] = rstd[q] * __builtin_fmaf(-xv[q][i][e], sgx[q], gv[q][i][e] - sg[q]);
                     if (res) {                                      // the residual branch's gradient joins here (was a separate add pass)
                         const f32x4 rv = *reinterpret_cast<const f32x4*>(res + row[q] * d + c * 4);
 #pragma unroll
@@ -1035,7 +1040,8 @@ int vf_layernorm_bwd_f32(const float* dy, const float* x, const float* gamma, fl
     const unsigned blocks = (unsigned)((rows + rpb - 1) / rpb);
     hipStream_t s = (hipStream_t)stream;
     __bf16* d16 = reinterpret_cast<__bf16*>(dx_bf16);
-    // Two rows of a wave in flight (62 us against 68-70 for one row at the training shape; vf_select(VF_SEL_LN_BWD_TWO_ROWS, 0) selects the one-row form, same bits).
+    // Two rows of a wave in flight (62 us against 68-70 for one row at the training shape; vf_select(VF_SEL_LN_BWD_TWO_ROWS, 0) selects the one-row form, same bits: the kernel spells its contraction out,
+    // tests/test_hip_transformer_kernels.py compares the two forms at every width).
     // History of this switch (round 3): with the wave sums on ds_bpermute (vf_wave_sum) the two-row form was bit-identical in a process that
     // owns the GPU but NOT bit-reproducible when a second process shared the device — the 2-rank gloo test on one GPU failed every other
     // run; tools/flaky_probe2.py traced it to ~1 call in 75 returning a few rows of dx ~1e-4 off on identical inputs (0 of 6 000 calls with
