@@ -326,6 +326,32 @@ int vf_argmax_rows_f32(const float* x, int64_t rows, int n, int ld, int64_t* idx
  * (VF_ERR_UNSUPPORTED otherwise: compute the logits and call vf_argmax_rows_f32). */
 int vf_lmhead_argmax_bf16(const void* h, int h_bf16, int64_t ldh, const void* w_packed, int64_t M, int K, int N, int64_t* idx,
                           float* max_logit, void* stream);
+/* tied LM head with the soft-max statistics fused into its epilogue (bf16 arm; csrc/lmhead_score.hip): the token log-likelihood of given
+ * codes, the prediction's confidence and its entropy without writing the [M][N] logits.  h, h_bf16, ldh, w_packed, M, K, N as
+ * vf_lmhead_argmax_bf16; target (NULL or int32 [M]).  With z[m][n] = sum_k bf16(h[m][k]) * bf16(W[n][k]), per row m (each output NULL or [M],
+ * at least one given):
+ *   idx, max_logit  first arg-max and its logit: the bits vf_lmhead_argmax_bf16 gives (ties -> lowest index)
+ *   target_logit    z[m][target[m]]: the bits vf_gemm_bf16 stores on that packing; -inf for a target outside [0, N) (nothing is read for it)
+ *   lse             max + log sum_n exp(z - max)
+ *   entropy         lse - sum_n p z, p = exp(z - lse), evaluated as log s - t / s from s = sum e^(z-max), t = sum (z-max) e^(z-max)
+ * One workgroup = 32 rows x all codes; every lane keeps an online (max, s, t) per accumulator row, merged in a fixed order (xor butterfly
+ * over the 32 code lanes, then waves 0..3), no atomics, no workspace: a row's outputs are bit-identical whatever M is, wherever the row
+ * sits and whichever outputs are requested.  Footprint: reads K elements of each of the M rows of h, the packing, M targets; writes M
+ * elements of each output given.  NULL h / w_packed, no output, target_logit without target, M < 0, K <= 0, N <= 0, ldh < K:
+ * VF_ERR_BAD_ARG.  Supported: K in {128, 768}, N % 128 == 0, ldh % 4 == 0 (fp32 rows) / % 8 == 0 (bf16 rows); anything else is
+ * VF_ERR_UNSUPPORTED (compute the logits and call vf_logits_score_f32); both before any launch.  M == 0 is a no-op. */
+int vf_lmhead_score_bf16(const void* h, int h_bf16, int64_t ldh, const void* w_packed, int64_t M, int K, int N, const int32_t* target,
+                         int64_t* idx, float* max_logit, float* lse, float* target_logit, float* entropy, void* stream);
+/* the same five statistics from materialised fp32 logits [rows][ld] (any N >= 1, ld >= N; columns N..ld-1 are not read): one wave per
+ * row, two passes (max / first index, then the sums from lane-strided partials and a fixed butterfly), same optional outputs.  -inf logits
+ * count as probability 0; a row of nothing but -inf has idx 0, max_logit = lse = -inf and entropy NaN.  Argument errors as above. */
+int vf_logits_score_f32(const float* logits, int64_t rows, int N, int64_t ld, const int32_t* target, int64_t* idx, float* max_logit,
+                        float* lse, float* target_logit, float* entropy, void* stream);
+/* per-view summary of those row statistics, `views` views of L rows each (all inputs [views * L], all required): token_log_prob =
+ * target_logit - lse and confidence = max_logit - lse per row [views * L]; log_likelihood = the sum of a view's token_log_prob in token
+ * order (one fp32 chain) and accuracy = the share of its rows with idx == target, [views] each.  One wave per view. */
+int vf_score_views_f32(const float* target_logit, const float* lse, const float* max_logit, const int64_t* idx, const int32_t* target,
+                       int64_t views, int L, float* token_log_prob, float* confidence, float* log_likelihood, float* accuracy, void* stream);
 /* host-side CRC-32C (Castagnoli) of a HOST buffer, for the TFRecord / TensorBundle files of the reference's datasets and
  * Keras checkpoints (viewformer_amd/codes_dataset.py, checkpoint.py); crc = 0 starts a new checksum */
 uint32_t vf_crc32c(const void* data, size_t n, uint32_t crc);

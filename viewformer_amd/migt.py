@@ -224,6 +224,20 @@ class MIGT:
             return None
         return ops.lmhead_argmax_bf16(h, self._lm_head16, M, c.d_model, c.n_embeddings)
 
+    def _lm_score(self, hf, M, target=None, fused: bool = False, want=ops.SCORE_OUTPUTS):
+        """soft-max statistics of the tied LM head per row (ops.SCORE_OUTPUTS: first arg-max, its logit, log-sum-exp, the logit of
+        ``target`` int32 [M], entropy) -> dict of [M] tensors.  Default: ``_lm`` then the row kernel on its logits (ops.logits_score).
+        ``fused=True`` on the bf16 arm at a supported shape: the statistics in the head's epilogue, the logits never written
+        (csrc/lmhead_score.hip) — measured slower than the default on the MI355X at 64 and at 8192 rows (every workgroup
+        streams the whole packed wte), hence not the default; on every other arm and shape ``fused=True`` takes the default route.  There
+        is no third route."""
+        c = self.config
+        if fused and getattr(self, '_lm_head16', None) is not None and ops.lmhead_score_supported(c.d_model, c.n_embeddings):
+            return ops.lmhead_score_bf16(hf, self._lm_head16, M, c.d_model, c.n_embeddings, target=target, want=want)
+        lg = torch.empty((M, c.n_embeddings), dtype=torch.float32, device=hf.device)
+        self._lm(hf, M, lg)                                                  # migt.py:417
+        return ops.logits_score(lg, M, c.n_embeddings, target=target, want=want)
+
     def _pose_embed(self, poses):
         """pose_embedding(get_model_input(poses)) — migt.py:139-145,291,354 (fp32; multiplier 1 at inference)"""
         B, Sp, _ = poses.shape
@@ -355,14 +369,18 @@ class MIGT:
             h = self._gemm(f, p + '.mlp.c_proj', M, res=h)
         return ops.layernorm(h, *self._ln['ln_f'], M, d)                     # migt.py:408
 
-    def generate_from_context(self, cache, query_cameras, codes_only: bool = True):
+    def generate_from_context(self, cache, query_cameras, codes_only: bool = True, return_confidence: bool = False):
         """N novel views per scene from a prefilled context: ``query_cameras`` fp32 [B,N,7] in the context's (relative, normalised)
         frame -> generated code maps int64 [B,N,t,t], or with ``codes_only=False`` the logits [B,N,t,t,n_embeddings].  Every query is
         a MASK view with its pose embedding — the last view of ``model(dict(input_ids=[ctx, MASK], poses=[ctx, query]))`` — whose
         rows go through the same LayerNorm / dense launches as there (on B*N*L rows) and whose attention reads the context's keys and
-        values from the cache (ops.attn_prefix).  Queries are independent of each other: a query's rows do not depend on N."""
+        values from the cache (ops.attn_prefix).  Queries are independent of each other: a query's rows do not depend on N.
+        ``return_confidence`` (with ``codes_only``): (codes, confidence, entropy), the last two fp32 [B,N,t,t] — log p of the generated
+        code (max logit - lse) and the entropy of the token's distribution, from the same LM-head launch (``_lm_score``)."""
         if not isinstance(cache, ContextCache):
             raise TypeError('generate_from_context: a ContextCache from prefill_context expected')
+        if return_confidence and not codes_only:
+            raise ValueError('generate_from_context: return_confidence goes with codes_only=True (the logits say it all)')
         cache.check(self)
         c, dev = self.config, self.device
         query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
@@ -375,11 +393,17 @@ class MIGT:
         d, H, nE = c.d_model, c.n_head, c.n_embeddings
         M = B * N * L
         if N == 0:
+            if return_confidence:
+                return (torch.empty((B, 0, *tshape), dtype=torch.int64, device=dev), torch.empty((B, 0, *tshape), dtype=torch.float32, device=dev),
+                        torch.empty((B, 0, *tshape), dtype=torch.float32, device=dev))
             return (torch.empty((B, 0, *tshape), dtype=torch.int64, device=dev) if codes_only
                     else torch.empty((B, 0, *tshape, nE), dtype=torch.float32, device=dev))
         add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
         ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
         hf = self._query_rows(cache, ids32, add, N)
+        if return_confidence:
+            st = self._lm_score(hf, M, want=('idx', 'max_logit', 'lse', 'entropy'))
+            return st['idx'].view(B, N, *tshape), (st['max_logit'] - st['lse']).view(B, N, *tshape), st['entropy'].view(B, N, *tshape)
         gen = self._lm_argmax(hf, M) if codes_only else None
         if gen is None:
             lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
@@ -388,6 +412,49 @@ class MIGT:
                 return lg.view(B, N, *tshape, nE)
             gen = ops.argmax_rows(lg, M, nE)
         return gen.view(B, N, *tshape)
+
+    def score_from_context(self, cache, query_cameras, codes, fused: bool = False):
+        """How well do photos fit cameras?  ``query_cameras`` fp32 [B,N,7] in the context's (relative, normalised) frame, ``codes`` int
+        [B,N,t,t] (one photo per camera) or [B,1,t,t] (one photo per scene against N candidate cameras) -> dict of
+            token_log_prob  fp32 [B,N,t,t]   log p(code) under the MASK view at that camera: target logit - lse
+            log_likelihood  fp32 [B,N]       its sum over a view's tokens, in token order
+            predicted_codes int64 [B,N,t,t]  what generate_from_context generates there
+            confidence      fp32 [B,N,t,t]   log p of the predicted code: max logit - lse
+            entropy         fp32 [B,N,t,t]   of the token's distribution (nats)
+            accuracy        fp32 [B,N]       share of a view's tokens where the prediction is the photo's code
+        Every camera is a MASK view exactly as in ``generate_from_context`` (same pose embedding, same ``_query_rows`` launches); the LM
+        head then yields five numbers per row (``_lm_score``: through the logits and the row kernel; ``fused=True``: in the bf16 head's
+        epilogue without the logits, the slower route on the MI355X, kept for A/B runs and tests).  A code outside [0, n_embeddings) has log-probability -inf.  Views are independent: a view's results do not depend on N."""
+        if not isinstance(cache, ContextCache):
+            raise TypeError('score_from_context: a ContextCache from prefill_context expected')
+        B, tshape = cache.B, cache.tshape
+        L = int(np.prod(tshape))
+        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
+        cache.check(self)
+        c, dev = self.config, self.device
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
+            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        codes = torch.as_tensor(codes).to(dev)
+        if (codes.dim() != 2 + len(tshape) or codes.shape[0] != B or codes.shape[1] not in (1, N) or tuple(codes.shape[2:]) != tshape
+                or codes.dtype.is_floating_point or codes.dtype == torch.bool):
+            raise ValueError(f'codes int [B={B},N={N} or 1,{",".join(map(str, tshape))}] expected, got {codes.dtype} {tuple(codes.shape)}')
+        d = c.d_model
+        M = B * N * L
+        if N == 0:
+            e4 = lambda dt: torch.empty((B, 0, *tshape), dtype=dt, device=dev)
+            e2 = lambda: torch.empty((B, 0), dtype=torch.float32, device=dev)
+            return dict(token_log_prob=e4(torch.float32), log_likelihood=e2(), predicted_codes=e4(torch.int64), confidence=e4(torch.float32),
+                        entropy=e4(torch.float32), accuracy=e2())
+        target = codes.to(torch.int32).expand(B, N, *tshape).reshape(M).contiguous()
+        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
+        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
+        hf = self._query_rows(cache, ids32, add, N)
+        st = self._lm_score(hf, M, target, fused=fused)
+        tlp, conf, ll, acc = ops.score_views(st, target, B * N, L)           # log-likelihood: one fp32 chain per view, in token order
+        return dict(token_log_prob=tlp.view(B, N, *tshape), log_likelihood=ll.view(B, N), predicted_codes=st['idx'].view(B, N, *tshape),
+                    confidence=conf.view(B, N, *tshape), entropy=st['entropy'].view(B, N, *tshape), accuracy=acc.view(B, N))
 
     def localize_from_context(self, cache, codes, return_tokens: bool = False, fused_tail: bool = True):
         """Localize N photos per scene against a prefilled context: ``codes`` int [B,N,t,t] (the photos' code maps) -> cameras fp32

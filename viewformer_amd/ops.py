@@ -679,6 +679,65 @@ def lmhead_argmax_bf16(h, w_packed_bf16, M, K, N, want_max=False):
     return (idx, mx) if want_max else idx
 
 
+SCORE_OUTPUTS = ('idx', 'max_logit', 'lse', 'target_logit', 'entropy')
+
+
+def _score_want(want, target):
+    want = tuple(want)
+    if not want or any(w not in SCORE_OUTPUTS for w in want):
+        raise ValueError(f'want: a non-empty subset of {SCORE_OUTPUTS} expected, got {want}')
+    if 'target_logit' in want and target is None:
+        raise ValueError("want 'target_logit': target expected")
+    return want
+
+
+def _score_outputs(want, rows, dev, target):
+    if target is not None:
+        _chk(target, torch.int32, 'target')
+        if target.numel() != rows or not target.is_contiguous():
+            raise ValueError(f'target: {rows} contiguous int32 expected, got {tuple(target.shape)}')
+    return {w: torch.empty(rows, dtype=torch.int64 if w == 'idx' else torch.float32, device=dev) for w in want}
+
+
+def lmhead_score_supported(K, N):
+    return K in (128, 768) and N % 128 == 0
+
+
+def lmhead_score_bf16(h, w_packed_bf16, M, K, N, target=None, want=SCORE_OUTPUTS):
+    """fused tied LM head + soft-max statistics (bf16 arm): h [M][K] fp32 or bf16 rows, w_packed_bf16 = pack_dense_nk_bf16(wte, n_rows=N),
+    target int32 [M] or None.  Returns a dict of the outputs named in ``want`` (SCORE_OUTPUTS; idx int64, the rest fp32, [M] each); the
+    [M][N] logits are never materialised."""
+    want = _score_want(want, target)
+    h16 = h.dtype == torch.bfloat16
+    _chk(h, torch.bfloat16 if h16 else torch.float32, 'h')
+    out = _score_outputs(want, M, h.device, target)
+    check(_lib.load().vf_lmhead_score_bf16(_p(h), 1 if h16 else 0, h.stride(0), _p(_chk(w_packed_bf16, torch.bfloat16, 'w_packed')), M, K, N,
+                                           _p(target), *(_p(out.get(w)) for w in SCORE_OUTPUTS), _stream()), 'vf_lmhead_score_bf16')
+    return out
+
+
+def logits_score(logits, rows, N, target=None, want=SCORE_OUTPUTS, ld=None):
+    """the same statistics from materialised fp32 logits [rows][ld >= N] (the fp32-equivalent arms; shapes the fused kernel refuses)"""
+    want = _score_want(want, target)
+    _f32(logits, 'logits')
+    out = _score_outputs(want, rows, logits.device, target)
+    check(_lib.load().vf_logits_score_f32(_p(logits), rows, N, N if ld is None else ld, _p(target), *(_p(out.get(w)) for w in SCORE_OUTPUTS),
+                                          _stream()), 'vf_logits_score_f32')
+    return out
+
+
+def score_views(stats, target, views, L):
+    """per-view summary of lmhead_score_bf16 / logits_score results (all five outputs) for ``views`` views of L rows: (token_log_prob
+    [views*L], confidence [views*L], log_likelihood [views] summed in token order, accuracy [views]), fp32"""
+    dev = target.device
+    tlp, conf = (torch.empty(views * L, dtype=torch.float32, device=dev) for _ in range(2))
+    ll, acc = (torch.empty(views, dtype=torch.float32, device=dev) for _ in range(2))
+    check(_lib.load().vf_score_views_f32(_p(_f32(stats['target_logit'])), _p(_f32(stats['lse'])), _p(_f32(stats['max_logit'])),
+                                         _p(_chk(stats['idx'], torch.int64, 'idx')), _p(_chk(target, torch.int32, 'target')), views, L,
+                                         _p(tlp), _p(conf), _p(ll), _p(acc), _stream()), 'vf_score_views_f32')
+    return tlp, conf, ll, acc
+
+
 def postprocess_u8(x):
     x = _f32(x).contiguous()
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)

@@ -10,6 +10,7 @@ and values are computed once (``MIGT.prefill_context``) and each query is a sing
     r.set_context(images=frames_u8, cameras=cams)            # or codes=... (scene_bank.SceneBank.gather)
     out = r.render(query_cameras)                            # out['generated_images'] uint8 [B,N,H,W,3]
     est = r.localize(images=photos_u8)                       # est['generated_cameras'] fp32 [B,N,7], the caller's world frame
+    fit = r.score(candidate_cameras, images=photo_u8)        # fit['log_likelihood'] fp32 [B,N]: how well the photo fits each camera
 
 Contract: ``render(q)['generated_images'][b, n]`` is what ``generate_batch_predictions`` generates for the scene (context views of b...,
 any frame) with cameras (context cameras of b..., q[b, n]); ``localize(photos)['generated_cameras'][b, n]`` is what it returns as
@@ -72,6 +73,7 @@ class ViewRenderer:
         self.cache = None
         self.transform = None
         self.context_codes = None
+        self.fused_score = None            # score: None = MIGT.score_from_context's default route, True / False = the fused LM head / through the logits
         self.fused_tail = None             # localize: None = MIGT.localize_from_context's default tail, True / False = the fused / unfused one
 
     def set_context(self, images=None, cameras=None, codes=None):
@@ -102,11 +104,12 @@ class ViewRenderer:
         self.transform, self.context_codes = transform, codes
         return self
 
-    def render(self, query_cameras, max_views_per_call: int = None, return_codes: bool = False):
+    def render(self, query_cameras, max_views_per_call: int = None, return_codes: bool = False, return_confidence: bool = False):
         """``query_cameras`` [B,N,7] in the caller's world frame (the context's) -> dict(generated_images uint8 [B,N,H,W,3]); with
         ``return_codes`` also generated_codes int64 [B,N,t,t], logits fp32 [B,N,t,t,n_embeddings] and decoded (the decoder's fp32
         output [B,N,H,W,3]).  N is walked in chunks of whole views (``plan_view_chunks``); a view's result does not depend on the
-        chunking."""
+        chunking.  With ``return_confidence`` also confidence and entropy, fp32 [B,N,t,t] each: log p of every generated token and the
+        entropy of its distribution (which of a view's tokens the model was guessing), from the LM-head launch that generates the codes."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.render: set_context() first')
         tm, cm = self.transformer, self.codebook
@@ -119,12 +122,18 @@ class ViewRenderer:
         t = tm.config.token_image_size
         nE = tm.config.n_embeddings
         poses = query_poses(query_cameras, self.transform)
-        gen, lgs = [], []
+        gen, lgs, conf, ent = [], [], [], []
         for a, b in plan_view_chunks(N, B, max_views_per_call):
-            if return_codes:
+            if return_confidence and not return_codes:
+                g, cf, en = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True, return_confidence=True)
+                gen.append(g); conf.append(cf); ent.append(en)
+            elif return_codes:
                 lg = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=False)
                 lgs.append(lg)
                 gen.append(ops.argmax_rows(lg.view(-1, nE), B * (b - a) * t * t, nE).view(B, b - a, t, t))   # ties -> lowest index
+                if return_confidence:                      # the logits exist already: the row kernel on them
+                    st = ops.logits_score(lg.view(-1, nE), B * (b - a) * t * t, nE, want=('max_logit', 'lse', 'entropy'))
+                    conf.append((st['max_logit'] - st['lse']).view(B, b - a, t, t)); ent.append(st['entropy'].view(B, b - a, t, t))
             else:
                 gen.append(tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True))
         codes = torch.cat(gen, 1) if gen else torch.empty((B, 0, t, t), dtype=torch.int64, device=dev)
@@ -149,7 +158,52 @@ class ViewRenderer:
             res.update(generated_codes=codes,
                        logits=torch.cat(lgs, 1) if lgs else torch.empty((B, 0, t, t, nE), dtype=torch.float32, device=dev),
                        decoded=dec.view(B, N, *dec.shape[1:]))
+        if return_confidence:
+            e = torch.empty((B, 0, t, t), dtype=torch.float32, device=dev)
+            res.update(confidence=torch.cat(conf, 1) if conf else e, entropy=torch.cat(ent, 1) if ent else e.clone())
         return res
+
+    def score(self, query_cameras, images=None, codes=None, max_views_per_call: int = None):
+        """How well do photos fit cameras?  ``query_cameras`` [B,N,7] in the caller's world frame (the context's) and ``images`` uint8
+        [B,N,H,W,3] or [B,1,H,W,3] (host or device; resized for the encoder as the evaluators do, each photo encoded once) or ``codes``
+        int [B,N,t,t] or [B,1,t,t] (already encoded) -> ``MIGT.score_from_context``'s dict: token_log_prob, predicted_codes, confidence,
+        entropy [B,N,t,t]; log_likelihood, accuracy [B,N].  One photo per scene (a view axis of 1) is scored against all N cameras:
+        ranking candidate poses.  N is walked in chunks of whole views (``plan_view_chunks``); a view's result does not depend on the
+        chunking.  ``self.fused_score`` (None = the model's default route, True / False = the fused head / through the logits) is for A/B runs."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.score: set_context() first')
+        if (images is None) == (codes is None):
+            raise ValueError('score: exactly one of images / codes expected')
+        tm, cm = self.transformer, self.codebook
+        dev = cm.device
+        B = self.cache.B
+        t = tm.config.token_image_size
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
+            raise ValueError(f'score: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        if codes is None:
+            images = torch.as_tensor(images).to(dev)
+            if images.dim() != 5 or images.shape[0] != B or images.shape[1] not in (1, N):
+                raise ValueError(f'score: images [B={B},N={N} or 1,H,W,3] expected, got {tuple(images.shape)}')
+            P = images.shape[1]
+            codes = (cm.encode(_frames_for_encode(images, cm.config.image_size))[-1] if P
+                     else torch.empty((B, 0, t, t), dtype=torch.int32, device=dev))
+        else:
+            codes = torch.as_tensor(codes).to(dev)
+            if (codes.dim() != 4 or codes.shape[0] != B or codes.shape[1] not in (1, N) or tuple(codes.shape[2:]) != (t, t)
+                    or codes.dtype.is_floating_point):
+                raise ValueError(f'score: codes int [B={B},N={N} or 1,{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
+            P = codes.shape[1]
+        codes = codes.to(torch.int32).view(B, P, t, t)
+        poses = query_poses(query_cameras, self.transform)
+        kw = {} if self.fused_score is None else dict(fused=bool(self.fused_score))
+        one = P == 1 and N != 1
+        parts = [tm.score_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **kw)
+                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
+        if not parts:
+            parts = [tm.score_from_context(self.cache, poses, codes[:, :0], **kw)]      # N = 0: empty tensors of the right shapes
+        return {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
 
     def localize(self, images=None, codes=None, max_views_per_call: int = None, return_tokens: bool = False):
         """Estimate the cameras of N photos per scene against the context: ``images`` uint8 [B,N,H,W,3] (host or device; resized for
@@ -199,6 +253,14 @@ def render_views(transformer_model, codebook_model, images, cameras, query_camer
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``max_views_per_call``, ``return_codes``."""
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
     return r.render(query_cameras, **kw)
+
+
+def score_views(transformer_model, codebook_model, images, cameras, query_cameras, photos=None, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7], ``query_cameras`` [B,N,7] and ``photos`` uint8 [B,N,H,W,3] or
+    [B,1,H,W,3] -> ``ViewRenderer.score``'s dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``photo_codes``
+    (the photos' codes instead of ``photos``), ``max_views_per_call``."""
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    return r.score(query_cameras, images=photos, codes=kw.pop('photo_codes', None), **kw)
 
 
 def localize_views(transformer_model, codebook_model, images, cameras, photos=None, **kw):
