@@ -352,6 +352,29 @@ int vf_logits_score_f32(const float* logits, int64_t rows, int N, int64_t ld, co
  * order (one fp32 chain) and accuracy = the share of its rows with idx == target, [views] each.  One wave per view. */
 int vf_score_views_f32(const float* target_logit, const float* lse, const float* max_logit, const int64_t* idx, const int32_t* target,
                        int64_t views, int L, float* token_log_prob, float* confidence, float* log_likelihood, float* accuracy, void* stream);
+/* S reproducible draws per row of fp32 logits [rows][ld >= N] under temperature, top-k and top-p (csrc/sample_rows.hip): one wave per row,
+ * the row read once into registers for N <= 1024.  Per row z, sample s < S and row_id (row_id[r], or r where row_id is NULL):
+ *   y_n = z_n / temperature; a -inf logit has probability 0 and is never kept;
+ *   top-k (top_k >= 1 and below the number of finite logits, else skipped): keep {n : y_n >= the k-th largest value}, ties all kept;
+ *   top-p (top_p < 1, else skipped) on that set: keep {n : y_n >= v*}, v* the largest value of the row at which the mass
+ *     sum_{kept, y_n >= v} e^(y_n - max y) reaches top_p x the mass top-k left (the smallest prefix of the descending order that reaches
+ *     top_p, ties at its last value kept; the maximum is always kept);
+ *   noise: key = vf_dropout_hash(seed, 0x5A0000 + s, row_id), w_n = lowbias32(n ^ key), u_n = ((w_n >> 9) + 0.5) 2^-23,
+ *     g_n = -log(-log u_n)   (csrc/vf_common.h; restated in viewformer_amd/_hash.py);
+ *   idx[r][s] = arg-max over the kept n of y_n + g_n, the lowest index on equal keys (Gumbel-max: an exact draw from the soft-max over
+ *     the kept set); logp[r][s] (NULL or [rows][S]) = log of its probability under that distribution, y_idx - (max y + log sum_kept
+ *     e^(y_n - max y)); kept[r] (NULL or [rows]) = the size of the kept set; thr[r] (NULL or [rows]) = the smallest kept y.
+ * A row without a finite logit gives idx -1, logp NaN, kept 0, thr NaN; NaN logits are unspecified.  A row's outputs depend on its
+ * logits, the parameters, seed and row_id only: not on rows, on where the row sits, on ld, on S (sample s of any launch is sample s)
+ * or on the outputs requested.  Footprint: reads columns 0..N-1 of each row and rows row_ids; writes rows x S elements of idx / logp and
+ * rows of kept / thr.  NULL logits / idx, rows < 0, N < 1, ld < N, temperature <= 0 or not finite, top_p <= 0 or NaN, top_k < 0,
+ * S < 1 or S > 65535: VF_ERR_BAD_ARG; N > 65536: VF_ERR_UNSUPPORTED; both before any launch.  rows == 0 is a no-op. */
+int vf_sample_rows_f32(const float* logits, int64_t rows, int N, int64_t ld, float temperature, int top_k, float top_p, uint32_t seed,
+                       const int64_t* row_id, int S, int64_t* idx, float* logp, int32_t* kept, float* thr, void* stream);
+/* log-likelihood of sampled views: logp [views * L][S] (vf_sample_rows_f32's) -> log_likelihood [views][S], the sum over a view's L
+ * tokens as ONE fp32 chain in token order per (view, sample).  One wave per (view, sample).  NULL pointers, views < 0, L < 1, S < 1 or
+ * S > 65535: VF_ERR_BAD_ARG.  views == 0 is a no-op. */
+int vf_sample_views_f32(const float* logp, int64_t views, int L, int S, float* log_likelihood, void* stream);
 /* host-side CRC-32C (Castagnoli) of a HOST buffer, for the TFRecord / TensorBundle files of the reference's datasets and
  * Keras checkpoints (viewformer_amd/codes_dataset.py, checkpoint.py); crc = 0 starts a new checksum */
 uint32_t vf_crc32c(const void* data, size_t n, uint32_t crc);

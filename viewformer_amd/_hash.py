@@ -9,10 +9,20 @@ so every element's keep probability is exactly 1 - floor(rate 2^32) / 2^32 (a ro
 holds the four elements of a group pays for one hash.  Group index and position of an element:
     [M][N] activations (embedding / residual / MLP sites):  g = (m >> 2) * N + n,  j = m & 3    (four consecutive ROWS of a column:
         what a lane of the GEMM epilogue holds);
-    attention weights (b, h, q, k) of a T-token sequence:  g = ((b H + h) << 32) | (q * ceil(T / 4) + (k >> 2)),  j = k & 3."""
+    attention weights (b, h, q, k) of a T-token sequence:  g = ((b H + h) << 32) | (q * ceil(T / 4) + (k >> 2)),  j = k & 3.
+
+Sampling noise (csrc/sample_rows.hip: vf_sample_rows_f32), built from the same two hashes: code n of the row with 64-bit ``row_id``, sample
+s (0 <= s < 65536) gets
+    key = vf_dropout_hash(seed, SITE_SAMPLE + s, row_id)        SITE_SAMPLE = 0x5A0000
+    w_n = lowbias32(n ^ key)
+    u_n = ((w_n >> 9) + 0.5) * 2^-23                            strictly inside (0, 1), exact in fp32 (and 1 - u_n is, too)
+    g_n = -log(-log u_n)                                        standard Gumbel noise
+and the draw is the arg-max over the kept codes of logit / temperature + g (Gumbel-max: an exact draw from their soft-max).  A token's
+noise depends on (seed, row_id, s, n) and on nothing else: not on the launch's geometry, the number of samples or the chunking."""
 import numpy as np
 
 _M = 0xFFFFFFFF
+SITE_SAMPLE = 0x5A0000
 
 
 def dropout_hash(seed, site, idx):
@@ -75,3 +85,22 @@ def attn_group(plane, q, k, T):
     stride = np.uint64((T + 3) // 4)
     g = (np.asarray(plane, dtype=np.uint64) << np.uint64(32)) | (np.asarray(q, dtype=np.uint64) * stride + (k >> np.uint64(2)))
     return g, np.broadcast_to(k & np.uint64(3), g.shape)
+
+
+def sample_key(seed, row_id, s):
+    """the 32-bit key of sample ``s`` of the row with 64-bit ``row_id``"""
+    if not 0 <= int(s) < 65536:
+        raise ValueError(f'sample_key: 0 <= s < 65536 expected, got {s}')
+    return int(dropout_hash(seed, SITE_SAMPLE + int(s), [int(row_id) & 0xFFFFFFFFFFFFFFFF])[0])
+
+
+def sample_uniform(seed, row_id, s, N):
+    """u_n for n < N, float64 holding the exact fp32 values ((w_n >> 9) + 0.5) * 2^-23"""
+    w = lowbias32(np.arange(N, dtype=np.uint64) ^ np.uint64(sample_key(seed, row_id, s)))
+    return ((w >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+
+
+def sample_gumbel(seed, row_id, s, N):
+    """g_n = -log(-log u_n) in float64 from the exact u (-log u through log1p of the exact 1 - u: accurate where u is close to 1)"""
+    u = sample_uniform(seed, row_id, s, N)
+    return -np.log(-np.log1p(-(1.0 - u)))

@@ -26,21 +26,11 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BN = 128;                   // the bf16 weight packing's chunk / n-block (csrc/gemm_bf16.hip)
 
-// e^d for d <= 0 to ~1.5 ulp on the hardware exp2 (vf_swish_1ulp's scheme): d log2(e) carried as hi + lo, e^d = 2^hi (1 + lo ln 2).
-// d = 0 gives exactly 1.  Results below the normal range flush to 0 (terms 2^-126 below the row's maximum term, which is 1).
-__device__ __forceinline__ float exp_neg(float d) {
-    const float LH = 1.4426950408889634f, LL = 1.9259629911266175e-8f;        // log2(e) = LH + LL
-    const float th = __fmul_rn(d, LH);
-    const float tl = __builtin_fmaf(d, LH, -th) + d * LL;
-    const float e0 = __builtin_amdgcn_exp2f(th);
-    return __builtin_fmaf(e0 * tl, 0.6931471805599453f, e0);
-}
-
 // (max, first index, s, t) of one set of codes absorbs another's: the side with the smaller maximum is rescaled by e^-(difference).
 // Symmetric (both partners of a butterfly step end with the same bits): the sums are commutative, equal maxima rescale by exactly 1.
 __device__ __forceinline__ void merge(float& m, int& i, float& s, float& t, float om, int oi, float os, float ot) {
     const float d = -fabsf(__fsub_rn(m, om));
-    const float e = exp_neg(d);
+    const float e = vf_exp_neg(d);
     const bool other_wins = om > m;
     const float ls = other_wins ? s : os, lt = other_wins ? t : ot;           // the lower side, to be rescaled
     const float hs = other_wins ? os : s, ht = other_wins ? ot : t;
@@ -117,7 +107,7 @@ __global__ __launch_bounds__(256, 1) void lmhead_score_kernel(const void* __rest
                 const float z = acc[r];
                 const bool up = z > best[r];                                    // strict: the first maximum of this lane's (ascending) codes
                 const float d = -fabsf(__fsub_rn(z, best[r]));
-                const float e = exp_neg(d);
+                const float e = vf_exp_neg(d);
                 const float s_up = __fadd_rn(__fmul_rn(sum[r], e), 1.f);        // the maximum moves by d: rescale, then the new code's (1, 0)
                 const float t_up = __fmul_rn(__fadd_rn(tsum[r], __fmul_rn(d, sum[r])), e);
                 const float s_dn = __fadd_rn(sum[r], e);

@@ -50,6 +50,16 @@ __device__ __forceinline__ float vf_swish_1ulp(float v) {
     return v * r;
 }
 
+// e^d for d <= 0 to ~1.5 ulp on the hardware exp2 (vf_swish_1ulp's scheme; the soft-max sums of lmhead_score.hip and sample_rows.hip): d log2(e) carried as hi + lo, e^d = 2^hi (1 + lo ln 2).
+// d = 0 gives exactly 1.  Results below the normal range flush to 0 (terms 2^-126 below the row's maximum term, which is 1).
+__device__ __forceinline__ float vf_exp_neg(float d) {
+    const float LH = 1.4426950408889634f, LL = 1.9259629911266175e-8f;        // log2(e) = LH + LL
+    const float th = __fmul_rn(d, LH);
+    const float tl = __builtin_fmaf(d, LH, -th) + d * LL;
+    const float e0 = __builtin_amdgcn_exp2f(th);
+    return __builtin_fmaf(e0 * tl, 0.6931471805599453f, e0);
+}
+
 __device__ __forceinline__ float vf_gelu_erf(float v) {
     // tf.nn.gelu(approximate=False): 0.5 x (1 + erf(x / sqrt 2))
     return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));

@@ -15,6 +15,7 @@ bias / exact-erf GELU / residual epilogues, tied LM head.  torch = memory + stre
 """
 from collections import OrderedDict
 
+import math
 import os
 
 import numpy as np
@@ -455,6 +456,66 @@ class MIGT:
         tlp, conf, ll, acc = ops.score_views(st, target, B * N, L)           # log-likelihood: one fp32 chain per view, in token order
         return dict(token_log_prob=tlp.view(B, N, *tshape), log_likelihood=ll.view(B, N), predicted_codes=st['idx'].view(B, N, *tshape),
                     confidence=conf.view(B, N, *tshape), entropy=st['entropy'].view(B, N, *tshape), accuracy=acc.view(B, N))
+
+    def sample_from_context(self, cache, query_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                            seed: int = 0, view0: int = 0, return_logits: bool = False):
+        """Draw S = ``n_samples`` code maps per query view from the model's distribution: ``query_cameras`` fp32 [B,N,7] in the context's
+        (relative, normalised) frame -> dict of
+            codes           int64 [B,N,S,t,t]  the draws
+            token_log_prob  fp32  [B,N,S,t,t]  log p of each drawn code under the distribution it was drawn from (after the filters)
+            log_likelihood  fp32  [B,N,S]      its sum over a view's tokens, in token order
+            kept            int32 [B,N,t,t]    the size of the set each token was drawn from
+        (``return_logits`` adds logits fp32 [B,N,t,t,n_embeddings]).  A MASK view's tokens are predicted in one pass and are independent
+        of each other given the context, so the S samples share ONE transformer view and one set of logits — the bits of
+        ``generate_from_context(codes_only=False)``: same pose embedding, ``_query_rows`` and ``_lm`` launches — followed by one row
+        kernel (ops.sample_rows: temperature, top-k, top-p and the S Gumbel-max draws).  ``top_k = 1`` gives ``generate_from_context``'s
+        codes whatever the seed.  The noise of token l of view n of scene b is keyed by (seed, row_id = (b << 32) | ((view0 + n) L + l),
+        sample index), b being the scene's number in the cache's batch: a token's draws do not depend on B, on N or on how the views are chunked (``view0`` = the number of the chunk's
+        first view)."""
+        if not isinstance(cache, ContextCache):
+            raise TypeError('sample_from_context: a ContextCache from prefill_context expected')
+        B, tshape = cache.B, cache.tshape
+        L = int(np.prod(tshape))
+        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
+        cache.check(self)
+        c, dev = self.config, self.device
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
+            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        S, view0 = int(n_samples), int(view0)
+        if not 1 <= S <= 65535:
+            raise ValueError(f'sample_from_context: 1 <= n_samples <= 65535 expected, got {n_samples}')
+        if not (float(temperature) > 0 and math.isfinite(float(temperature))) or not float(top_p) > 0 or int(top_k) < 0:
+            raise ValueError(f'sample_from_context: temperature > 0 (finite), top_p > 0 and top_k >= 0 expected, got {temperature}, {top_p}, {top_k}')
+        if view0 < 0 or (view0 + N) * L >= 1 << 32:
+            raise ValueError(f'sample_from_context: 0 <= view0 and (view0 + N) * {L} < 2^32 expected, got view0 = {view0}, N = {N}')
+        d, nE = c.d_model, c.n_embeddings
+        M = B * N * L
+        if N == 0:
+            res = dict(codes=torch.empty((B, 0, S, *tshape), dtype=torch.int64, device=dev),
+                       token_log_prob=torch.empty((B, 0, S, *tshape), dtype=torch.float32, device=dev),
+                       log_likelihood=torch.empty((B, 0, S), dtype=torch.float32, device=dev),
+                       kept=torch.empty((B, 0, *tshape), dtype=torch.int32, device=dev))
+            if return_logits:
+                res['logits'] = torch.empty((B, 0, *tshape, nE), dtype=torch.float32, device=dev)
+            return res
+        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
+        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
+        hf = self._query_rows(cache, ids32, add, N)
+        lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
+        self._lm(hf, M, lg)                                                  # migt.py:417
+        row_id = ((torch.arange(B, dtype=torch.int64, device=dev) << 32).view(B, 1)
+                  + (torch.arange(N * L, dtype=torch.int64, device=dev) + view0 * L).view(1, N * L)).reshape(M).contiguous()
+        st = ops.sample_rows(lg, M, nE, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, row_id=row_id, n_samples=S,
+                             want=('idx', 'logp', 'kept'))
+        ll = ops.sample_views(st['logp'], B * N, L, S)                      # one fp32 chain per (view, sample), in token order
+        res = dict(codes=st['idx'].view(B, N, L, S).permute(0, 1, 3, 2).reshape(B, N, S, *tshape),
+                   token_log_prob=st['logp'].view(B, N, L, S).permute(0, 1, 3, 2).reshape(B, N, S, *tshape),
+                   log_likelihood=ll.view(B, N, S), kept=st['kept'].view(B, N, *tshape))
+        if return_logits:
+            res['logits'] = lg.view(B, N, *tshape, nE)
+        return res
 
     def localize_from_context(self, cache, codes, return_tokens: bool = False, fused_tail: bool = True):
         """Localize N photos per scene against a prefilled context: ``codes`` int [B,N,t,t] (the photos' code maps) -> cameras fp32

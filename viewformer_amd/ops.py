@@ -738,6 +738,49 @@ def score_views(stats, target, views, L):
     return tlp, conf, ll, acc
 
 
+SAMPLE_OUTPUTS = ('idx', 'logp', 'kept', 'thr')
+
+
+def sample_rows(logits, rows, N, temperature=1.0, top_k=0, top_p=1.0, seed=0, row_id=None, n_samples=1, ld=None, want=('idx', 'logp')):
+    """``n_samples`` reproducible draws per row of fp32 logits [rows][ld >= N] under temperature, top-k and top-p (vf_sample_rows_f32;
+    include/vf_hip.h has the definitions).  ``row_id`` int64 [rows] or None (the row's number) keys the noise together with ``seed`` and
+    the sample index.  Returns a dict of the outputs named in ``want`` (SAMPLE_OUTPUTS): idx int64 [rows, S], logp fp32 [rows, S] (log
+    probability of each draw under the filtered distribution), kept int32 [rows] (size of the set drawn from), thr fp32 [rows] (the
+    smallest kept logit / temperature)."""
+    want = tuple(want)
+    if not want or any(w not in SAMPLE_OUTPUTS for w in want):
+        raise ValueError(f'want: a non-empty subset of {SAMPLE_OUTPUTS} expected, got {want}')
+    _f32(logits, 'logits')
+    S = int(n_samples)
+    ldv = N if ld is None else int(ld)
+    if rows < 0 or N < 1 or ldv < N or not logits.is_contiguous() or logits.numel() < (rows - 1) * ldv + N * (rows > 0):
+        raise ValueError(f'logits: {rows} contiguous rows of {N} with ld {ldv} expected, got {tuple(logits.shape)}')
+    if row_id is not None:
+        _chk(row_id, torch.int64, 'row_id')
+        if row_id.numel() != rows or not row_id.is_contiguous():
+            raise ValueError(f'row_id: {rows} contiguous int64 expected, got {tuple(row_id.shape)}')
+    dev = logits.device
+    shapes = dict(idx=((rows, max(S, 0)), torch.int64), logp=((rows, max(S, 0)), torch.float32), kept=((rows,), torch.int32),
+                  thr=((rows,), torch.float32))
+    out = {w: torch.empty(shapes[w][0], dtype=shapes[w][1], device=dev) for w in SAMPLE_OUTPUTS if w == 'idx' or w in want}
+    check(_lib.load().vf_sample_rows_f32(_p(logits), rows, N, N if ld is None else ld, float(temperature), int(top_k), float(top_p),
+                                         int(seed) & 0xFFFFFFFF, _p(row_id), S, *(_p(out.get(w)) for w in SAMPLE_OUTPUTS), _stream()),
+          'vf_sample_rows_f32')
+    return {w: out[w] for w in want}
+
+
+def sample_views(logp, views, L, n_samples):
+    """log-likelihood of sampled views: ``logp`` fp32 [views * L, S] (sample_rows') -> fp32 [views, S], each the sum over the view's L
+    tokens as one fp32 chain in token order"""
+    _f32(logp, 'logp')
+    S = int(n_samples)
+    if logp.numel() != views * L * S or not logp.is_contiguous():
+        raise ValueError(f'logp: contiguous [{views * L}, {S}] expected, got {tuple(logp.shape)}')
+    ll = torch.empty((views, S), dtype=torch.float32, device=logp.device)
+    check(_lib.load().vf_sample_views_f32(_p(logp), views, L, S, _p(ll), _stream()), 'vf_sample_views_f32')
+    return ll
+
+
 def postprocess_u8(x):
     x = _f32(x).contiguous()
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)

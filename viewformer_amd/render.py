@@ -11,6 +11,7 @@ and values are computed once (``MIGT.prefill_context``) and each query is a sing
     out = r.render(query_cameras)                            # out['generated_images'] uint8 [B,N,H,W,3]
     est = r.localize(images=photos_u8)                       # est['generated_cameras'] fp32 [B,N,7], the caller's world frame
     fit = r.score(candidate_cameras, images=photo_u8)        # fit['log_likelihood'] fp32 [B,N]: how well the photo fits each camera
+    alt = r.sample(query_cameras, n_samples=8, top_p=0.9)    # alt['generated_images'] uint8 [B,N,8,H,W,3]: draws, with their log-likelihood
 
 Contract: ``render(q)['generated_images'][b, n]`` is what ``generate_batch_predictions`` generates for the scene (context views of b...,
 any frame) with cameras (context cameras of b..., q[b, n]); ``localize(photos)['generated_cameras'][b, n]`` is what it returns as
@@ -104,6 +105,30 @@ class ViewRenderer:
         self.transform, self.context_codes = transform, codes
         return self
 
+    def _decode(self, flat, keep_decoded: bool = False):
+        """code maps int [n,t,t] -> (images uint8 [n,H,W,3], the decoder's fp32 output [n,H,W,3] or None), decoded in chunks of
+        MAX_SCENES_PER_CALL maps as the evaluators do"""
+        cm = self.codebook
+        dev = cm.device
+        decs, imgs = [], []
+        for a in range(0, flat.shape[0], MAX_SCENES_PER_CALL):
+            dec = cm.decode_code(flat[a:a + MAX_SCENES_PER_CALL])
+            if cm.data_format == 'NCHW':
+                dec = dec.permute(0, 2, 3, 1)
+            dec = dec.contiguous()
+            imgs.append(ops.postprocess_u8(dec))
+            if keep_decoded:
+                decs.append(dec)
+        if imgs:
+            img = torch.cat(imgs) if len(imgs) > 1 else imgs[0]
+        else:
+            s = cm.config.image_size
+            img = torch.empty((0, s, s, 3), dtype=torch.uint8, device=dev)
+        if not keep_decoded:
+            return img, None
+        dec = torch.cat(decs) if len(decs) > 1 else (decs[0] if decs else torch.empty((0, *img.shape[1:]), dtype=torch.float32, device=dev))
+        return img, dec
+
     def render(self, query_cameras, max_views_per_call: int = None, return_codes: bool = False, return_confidence: bool = False):
         """``query_cameras`` [B,N,7] in the caller's world frame (the context's) -> dict(generated_images uint8 [B,N,H,W,3]); with
         ``return_codes`` also generated_codes int64 [B,N,t,t], logits fp32 [B,N,t,t,n_embeddings] and decoded (the decoder's fp32
@@ -137,30 +162,49 @@ class ViewRenderer:
             else:
                 gen.append(tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True))
         codes = torch.cat(gen, 1) if gen else torch.empty((B, 0, t, t), dtype=torch.int64, device=dev)
-        flat = codes.reshape(B * N, t, t)
-        decs, imgs = [], []
-        for a in range(0, B * N, MAX_SCENES_PER_CALL):
-            dec = cm.decode_code(flat[a:a + MAX_SCENES_PER_CALL])
-            if cm.data_format == 'NCHW':
-                dec = dec.permute(0, 2, 3, 1)
-            dec = dec.contiguous()
-            imgs.append(ops.postprocess_u8(dec))
-            if return_codes:
-                decs.append(dec)
-        if imgs:
-            img = torch.cat(imgs) if len(imgs) > 1 else imgs[0]
-        else:
-            s = cm.config.image_size
-            img = torch.empty((0, s, s, 3), dtype=torch.uint8, device=dev)
+        img, dec = self._decode(codes.reshape(B * N, t, t), keep_decoded=return_codes)
         res = dict(generated_images=img.view(B, N, *img.shape[1:]))
         if return_codes:
-            dec = torch.cat(decs) if len(decs) > 1 else (decs[0] if decs else torch.empty((0, *img.shape[1:]), dtype=torch.float32, device=dev))
             res.update(generated_codes=codes,
                        logits=torch.cat(lgs, 1) if lgs else torch.empty((B, 0, t, t, nE), dtype=torch.float32, device=dev),
                        decoded=dec.view(B, N, *dec.shape[1:]))
         if return_confidence:
             e = torch.empty((B, 0, t, t), dtype=torch.float32, device=dev)
             res.update(confidence=torch.cat(conf, 1) if conf else e, entropy=torch.cat(ent, 1) if ent else e.clone())
+        return res
+
+    def sample(self, query_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+               max_views_per_call: int = None, return_codes: bool = False):
+        """Draw ``n_samples`` = S plausible views per camera: ``query_cameras`` [B,N,7] in the caller's world frame (the context's) ->
+        dict(generated_images uint8 [B,N,S,H,W,3], log_likelihood fp32 [B,N,S]: the log-probability of each drawn code map under the
+        distribution it was drawn from); with ``return_codes`` also generated_codes int64 [B,N,S,t,t], token_log_prob fp32 [B,N,S,t,t]
+        and kept int32 [B,N,t,t] (the size of the set each token was drawn from).  ``temperature``, ``top_k`` and ``top_p`` trade
+        sharpness against diversity (``MIGT.sample_from_context``; ``top_k = 1`` is ``render``).  Draws are reproducible: they depend on
+        (seed, the scene's NUMBER b in this context's batch, view number, token, sample number) and not on the batch size, on N or on the
+        chunking — N is walked in chunks of whole views (``plan_view_chunks``) and a view's result does not depend on it.  Because the
+        noise is keyed by b, a scene set as the context alone (b = 0) and the same scene at b = 1 of a batch get DIFFERENT draws for one
+        seed (same distribution, same kept sets, same ``top_k = 1`` result); only scene 0 of a batch reproduces its stand-alone draws."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.sample: set_context() first')
+        tm, cm = self.transformer, self.codebook
+        dev = cm.device
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
+        B = self.cache.B
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
+            raise ValueError(f'sample: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        S = int(n_samples)
+        t = tm.config.token_image_size
+        poses = query_poses(query_cameras, self.transform)
+        kw = dict(n_samples=S, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+        parts = [tm.sample_from_context(self.cache, poses[:, a:b], view0=a, **kw) for a, b in plan_view_chunks(N, B, max_views_per_call)]
+        if not parts:
+            parts = [tm.sample_from_context(self.cache, poses, **kw)]               # N = 0: empty tensors of the right shapes
+        out = {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        img, _ = self._decode(out['codes'].reshape(B * N * S, t, t))
+        res = dict(generated_images=img.view(B, N, S, *img.shape[1:]), log_likelihood=out['log_likelihood'])
+        if return_codes:
+            res.update(generated_codes=out['codes'], token_log_prob=out['token_log_prob'], kept=out['kept'])
         return res
 
     def score(self, query_cameras, images=None, codes=None, max_views_per_call: int = None):
@@ -253,6 +297,14 @@ def render_views(transformer_model, codebook_model, images, cameras, query_camer
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``max_views_per_call``, ``return_codes``."""
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
     return r.render(query_cameras, **kw)
+
+
+def sample_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.sample``'s
+    dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``n_samples``, ``temperature``, ``top_k``, ``top_p``,
+    ``seed``, ``max_views_per_call``, ``return_codes``."""
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    return r.sample(query_cameras, **kw)
 
 
 def score_views(transformer_model, codebook_model, images, cameras, query_cameras, photos=None, **kw):
