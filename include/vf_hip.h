@@ -289,6 +289,24 @@ int vf_attn_prefix_bf16(const void* q, const void* k, const void* v, const void*
 int vf_attn_prefix_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
                          int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                          int ldo, void* stream);
+/* The same two kernels with a context length PER QUERY VIEW (ragged batches, context-size sweeps): ctx_len, a device pointer to [B*N]
+ * int32, view (b, n) attending to the first ctx_len[b*N+n] of the C cached views and to its own tile.  C is the cache's capacity: it bounds
+ * the lengths (the kernel clamps what it reads to [0, C], so no value takes it outside the cache) and fixes nothing else; prefix_stride
+ * addresses the cache as above.  Length 0: the view sees only itself.  The work layout is the fixed-C one: a workgroup stages the prefix tiles
+ * up to its longest member's length once, a wave consumes tile s only if s < its own length, own tiles follow; a wave's key order (prefix
+ * ascending, then its own view) and arithmetic are untouched.  Contract:
+ *   - a query view with length c >= 1 gets, bit for bit, what the fixed-C entry gives it with C = c on the same buffers and the same
+ *     prefix_stride, whatever the other views' lengths, N, or its position;
+ *   - the kernel writes exactly the logical output elements;
+ *   - its result for a view does not depend on cache rows at or beyond that view's length (they are read only where another view of the
+ *     same workgroup reaches them, and then not by this view's waves).
+ * The cost of a workgroup is that of its longest member.  Checks as above, and NULL ctx_len: VF_ERR_BAD_ARG. */
+int vf_attn_prefix_var_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
+                            int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                            int ldo, const int32_t* ctx_len, void* stream);
+int vf_attn_prefix_var_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
+                             int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                             int ldo, const int32_t* ctx_len, void* stream);
 /* Single-head spatial self-attention of the VQGAN AttnBlock, fused (csrc/attn_spatial.hip): replaces the core of AttnBlock.forward
  * (vqgan_th.py:124-141) — scores = q^T k * scale, softmax over the keys, h = v . p^T — per image of HW tokens x C channels, from the
  * fused q|k|v projection qkv [n_img * HW][ld] (q at column 0, k at C, v at 2C); out [n_img * HW][ldo].  Exact fp32

@@ -13,6 +13,17 @@
 // query's result is bit-identical whatever N, whatever the position of the view in the launch.  Keys are walked in ascending order, prefix
 // first, own view last — the order of the twin-mask pass — with the arithmetic of attention_lp.hip (bf16 arm: the same bits as its
 // register-staged kernel) and of attention_x6.hip (fp32-equivalent arm: the same bits).
+//
+// Variable context lengths (vf_attn_prefix_var_*, the kernels' VAR instantiation): a length per query view, ctx_len[b*N + n] in [0, C]
+// (clamped on read; C is the cache's capacity).  The layout above stays: the group walks gmax = the longest length among its own views, so
+// each prefix tile is still staged once; a wave consumes prefix tile s only if s < its own length and otherwise only helps staging; own
+// tiles follow at steps gmax, gmax + 1, ...  A group whose lengths are all 0 starts with an own tile.  A wave without a view (last partial
+// group) counts as length 0 and reads no length.  Contract:
+//   - a view with length c >= 1 gets, bit for bit, what the fixed-C entry gives it with C = c on the same buffers and prefix_stride,
+//     whatever the other views' lengths, N, or its position: its key order (prefix ascending, then own) and arithmetic are the same;
+//   - the kernel writes exactly the logical output elements;
+//   - a view's result does not depend on cache rows at or beyond its length.
+// The fixed-C instantiation compiles to what it was (gmax = mylen = C are the same value): same bits, same registers.
 #include "vf_common.h"
 #include "../../include/vf_hip.h"
 
@@ -35,7 +46,15 @@ struct prefix_args {
     int ldq, ldk, ldv, ldkp, ldvp, ldo;
     long long pstride;
     int in16, out16;
+    const int* ctx_len;                               // VAR only: [B*N] context lengths, one per query view
 };
+
+// VAR: the length of query view (b, n), clamped to the cache's capacity; fixed-C: C
+template <bool VAR>
+__device__ __forceinline__ int view_len(const prefix_args& a, size_t b, int n) {
+    if constexpr (VAR) return min(max(a.ctx_len[b * (size_t)a.N + (size_t)n], 0), a.C);
+    else return a.C;
+}
 
 __device__ __forceinline__ f32x4 load4(const void* base, size_t off, int in16) {
     if (in16) {
@@ -49,6 +68,7 @@ __device__ __forceinline__ f32x4 load4(const void* base, size_t off, int in16) {
 constexpr int K_LDB = 144;            // K row [key][dh] bf16: 128 B + 16 (conflict-free ds_read_b128)
 constexpr int VT_LDB = 136;           // V^T row [feature][key] bf16: 128 B + 8
 
+template <bool VAR>
 __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const prefix_args a) {
     __shared__ __attribute__((aligned(16))) unsigned char Ks[LV * K_LDB];
     __shared__ __attribute__((aligned(16))) unsigned char Vt[DH * VT_LDB];
@@ -82,19 +102,27 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const prefix_a
     // staging map: thread -> 4-feature column tid&15; K rows (tid>>4) + 16 i; V key pairs 2p, 2p+1 with p = (tid>>4) + 16 (i>>1)
     const int s_col4 = tid & 15;
     const int s_row0 = tid >> 4;
-    const int nsteps = a.C + nown;                               // C prefix tiles, then the group's own tiles
+    // VAR: the wave walks its own view's first mylen prefix tiles; the group stages gmax = its longest member's (a wave without a view
+    // counts as length 0 and reads no length)
+    int mylen = a.C, gmax = a.C;
+    if constexpr (VAR) {
+        gmax = 0;
+        for (int j = 0; j < nown; ++j) gmax = max(gmax, view_len<VAR>(a, b, v0 + j));
+        mylen = active ? view_len<VAR>(a, b, v0 + wave) : 0;
+    }
+    const int nsteps = gmax + nown;                              // gmax prefix tiles, then the group's own tiles
     f32x4 kreg[4], vreg[4];
     auto prefetch = [&](int s) {
         const void *kb, *vb;
         size_t k0, v0_;
         int ldk_, ldv_;
-        if (s < a.C) {
+        if (s < gmax) {
             kb = a.kp; vb = a.vp; ldk_ = a.ldkp; ldv_ = a.ldvp;
             k0 = b * (size_t)a.pstride + (size_t)s * LV * ldk_ + h * DH;
             v0_ = b * (size_t)a.pstride + (size_t)s * LV * ldv_ + h * DH;
         } else {
             kb = a.k; vb = a.v; ldk_ = a.ldk; ldv_ = a.ldv;
-            const size_t r0 = (b * (size_t)a.N + (size_t)(v0 + s - a.C)) * LV;
+            const size_t r0 = (b * (size_t)a.N + (size_t)(v0 + s - gmax)) * LV;
             k0 = r0 * ldk_ + h * DH;
             v0_ = r0 * ldv_ + h * DH;
         }
@@ -144,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const prefix_a
         stage();
         __syncthreads();
         if (s + 1 < nsteps) prefetch(s + 1);
-        if (!active || (s >= a.C && s - a.C != wave)) continue;      // an own tile belongs to one wave
+        if (!active || (s >= gmax ? s - gmax != wave : s >= mylen)) continue;      // an own tile belongs to one wave; a prefix tile to the views that reach it
 
         // ---- S^T = K . Q^T: each K fragment (LDS) feeds both query tiles
         f32x16 st[2][2];                                             // [query tile][key half]
@@ -251,6 +279,7 @@ __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l)
 constexpr int K6_LDB = 400;   // bytes per K row in LDS: 3 planes x 128 B + 16 B pad (attention_x6.hip)
 constexpr int VT6_LDB = 392;  // bytes per V^T row: 3 planes x 128 B + 8 B pad
 
+template <bool VAR>
 __global__ __launch_bounds__(256, 2) void attn_prefix_x6_kernel(const prefix_args a) {
     __shared__ __attribute__((aligned(16))) unsigned char Ks[LV * K6_LDB];
     __shared__ __attribute__((aligned(16))) unsigned char Vt[DH * VT6_LDB];
@@ -290,18 +319,24 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_x6_kernel(const prefix_arg
 
     const int s_col4 = tid & 15;
     const int s_row0 = tid >> 4;
-    const int nsteps = a.C + nown;
+    int mylen = a.C, gmax = a.C;                                 // as the bf16 arm
+    if constexpr (VAR) {
+        gmax = 0;
+        for (int j = 0; j < nown; ++j) gmax = max(gmax, view_len<VAR>(a, b, v0 + j));
+        mylen = active ? view_len<VAR>(a, b, v0 + slot) : 0;
+    }
+    const int nsteps = gmax + nown;
     f32x4 kreg[4], vreg[4];
     auto prefetch = [&](int s) {
         const float *kb, *vb;
         int ldk_, ldv_;
-        if (s < a.C) {
+        if (s < gmax) {
             ldk_ = a.ldkp; ldv_ = a.ldvp;
             kb = reinterpret_cast<const float*>(a.kp) + b * (size_t)a.pstride + (size_t)s * LV * ldk_ + h * DH;
             vb = reinterpret_cast<const float*>(a.vp) + b * (size_t)a.pstride + (size_t)s * LV * ldv_ + h * DH;
         } else {
             ldk_ = a.ldk; ldv_ = a.ldv;
-            const size_t r0 = (b * (size_t)a.N + (size_t)(v0 + s - a.C)) * LV;
+            const size_t r0 = (b * (size_t)a.N + (size_t)(v0 + s - gmax)) * LV;
             kb = reinterpret_cast<const float*>(a.k) + r0 * ldk_ + h * DH;
             vb = reinterpret_cast<const float*>(a.v) + r0 * ldv_ + h * DH;
         }
@@ -358,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_x6_kernel(const prefix_arg
         }
         __syncthreads();
         if (s + 1 < nsteps) prefetch(s + 1);
-        if (!active || (s >= a.C && s - a.C != slot)) continue;      // an own tile belongs to the two waves of its view
+        if (!active || (s >= gmax ? s - gmax != slot : s >= mylen)) continue;      // an own tile belongs to the two waves of its view
 
         // ---- S^T = K . Q^T
         f32x16 st[2];
@@ -470,6 +505,28 @@ int prefix_check(const prefix_args& a, int B, int H, int L, int dh) {
     return VF_OK;
 }
 
+template <bool VAR>
+int launch_bf16(const prefix_args& a, int B, int H, int L, int dh, void* stream) {
+    if (VAR && !a.ctx_len) return VF_ERR_BAD_ARG;
+    const int rc = prefix_check(a, B, H, L, dh);
+    if (rc != VF_OK) return rc;
+    if (B == 0 || a.N == 0) return VF_OK;
+    dim3 grid((unsigned)H, (unsigned)B, (unsigned)((a.N + GV16 - 1) / GV16));
+    hipLaunchKernelGGL(attn_prefix_bf16_kernel<VAR>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    return vf_last_status();
+}
+
+template <bool VAR>
+int launch_x6(const prefix_args& a, int B, int H, int L, int dh, void* stream) {
+    if (VAR && !a.ctx_len) return VF_ERR_BAD_ARG;
+    const int rc = prefix_check(a, B, H, L, dh);
+    if (rc != VF_OK) return rc;
+    if (B == 0 || a.N == 0) return VF_OK;
+    dim3 grid((unsigned)H, (unsigned)B, (unsigned)((a.N + GV32 - 1) / GV32));
+    hipLaunchKernelGGL(attn_prefix_x6_kernel<VAR>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    return vf_last_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -477,25 +534,31 @@ extern "C" {
 int vf_attn_prefix_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
                         int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                         int ldo, void* stream) {
-    const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0};
-    const int rc = prefix_check(a, B, H, L, dh);
-    if (rc != VF_OK) return rc;
-    if (B == 0 || N == 0) return VF_OK;
-    dim3 grid((unsigned)H, (unsigned)B, (unsigned)((N + GV16 - 1) / GV16));
-    hipLaunchKernelGGL(attn_prefix_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    return vf_last_status();
+    const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0,
+                        nullptr};
+    return launch_bf16<false>(a, B, H, L, dh, stream);
 }
 
 int vf_attn_prefix_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
                          int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                          int ldo, void* stream) {
-    const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, 0, 0};
-    const int rc = prefix_check(a, B, H, L, dh);
-    if (rc != VF_OK) return rc;
-    if (B == 0 || N == 0) return VF_OK;
-    dim3 grid((unsigned)H, (unsigned)B, (unsigned)((N + GV32 - 1) / GV32));
-    hipLaunchKernelGGL(attn_prefix_x6_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    return vf_last_status();
+    const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, 0, 0, nullptr};
+    return launch_x6<false>(a, B, H, L, dh, stream);
+}
+
+int vf_attn_prefix_var_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
+                            int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                            int ldo, const int32_t* ctx_len, void* stream) {
+    const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0,
+                        ctx_len};
+    return launch_bf16<true>(a, B, H, L, dh, stream);
+}
+
+int vf_attn_prefix_var_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
+                             int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                             int ldo, const int32_t* ctx_len, void* stream) {
+    const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, 0, 0, ctx_len};
+    return launch_x6<true>(a, B, H, L, dh, stream);
 }
 
 }  // extern "C"

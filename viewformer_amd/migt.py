@@ -344,10 +344,27 @@ class MIGT:
         self._blocks(codes, self._pose_embed(cameras), B, C, L, kv_sink=kv)
         return ContextCache(self, kv, B, C, tshape)
 
-    def _query_rows(self, cache, ids32, add, N):
+    def _context_lengths(self, cache, n_context, N):
+        """``n_context`` of the four ``*_from_context`` methods -> int32 device tensor [B*N] for ``_query_rows``, or None (None in:
+        every view sees all C cached views, the path and the launches without the keyword).  An int, [B] (one length per scene) or
+        [B,N] (one per query view) of integers in [0, cache.C]: the view sees that many leading context views and itself, which is the
+        model's answer for that context (0: no context at all).  Host data preferred (a device tensor is brought to the host once, to
+        validate it); anything else: ValueError, before any launch.  A group of 4 (bf16) / 2 (f32) consecutive views costs what its
+        longest member costs, and rows are not reordered here."""
+        if n_context is None:
+            return None
+        from .render import plan_context_lengths
+        plan = plan_context_lengths(n_context, cache.B, N, cache.C)
+        return torch.from_numpy(plan.reshape(-1)).to(self.device)
+
+    def _query_rows(self, cache, ids32, add, N, n_context=None):
         """The per-layer loop over the rows of N query views per scene of ``cache``: ``ids32`` int32 [B*N*L] token ids, ``add`` fp32
         [B*N, d] (a pose embedding or the LOC row per view) -> ln_f hidden states [B*N*L, d].  Each view attends to the cached context
-        and to itself (ops.attn_prefix); its rows go through the LayerNorm / dense launches of the full pass."""
+        and to itself (ops.attn_prefix); its rows go through the LayerNorm / dense launches of the full pass.  ``n_context``: None, or an
+        int32 device tensor [B*N] (``_context_lengths``): view (b, n) attends to the first ``n_context[b*N+n]`` cached views only — the
+        model's answer for a context of that many views, since the first c views of a C-view cache are the cache of those c views.
+        Rows are not reordered: the attention's workgroups take 4 (bf16) / 2 (f32) consecutive views, and a group costs what its
+        longest member costs."""
         c, dev = self.config, self.device
         B, C = cache.B, cache.C
         L = int(np.prod(cache.tshape))
@@ -363,21 +380,23 @@ class MIGT:
             self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
             ckv = cache.kv[i]                                                # [B*C*L, 3d], thirds (V, Q, K)
             ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
-                            3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16')
+                            3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
             h = self._gemm(att, p + '.attn.c_proj', M, res=h)
             m = ops.layernorm(h, *self._ln[p + '.ln_2'], M, d, out_bf16=act16)
             f = self._gemm(m, p + '.mlp.c_fc', M, epilogue=ops.EPI_GELU, out_bf16=act16)
             h = self._gemm(f, p + '.mlp.c_proj', M, res=h)
         return ops.layernorm(h, *self._ln['ln_f'], M, d)                     # migt.py:408
 
-    def generate_from_context(self, cache, query_cameras, codes_only: bool = True, return_confidence: bool = False):
+    def generate_from_context(self, cache, query_cameras, codes_only: bool = True, return_confidence: bool = False, n_context=None):
         """N novel views per scene from a prefilled context: ``query_cameras`` fp32 [B,N,7] in the context's (relative, normalised)
         frame -> generated code maps int64 [B,N,t,t], or with ``codes_only=False`` the logits [B,N,t,t,n_embeddings].  Every query is
         a MASK view with its pose embedding — the last view of ``model(dict(input_ids=[ctx, MASK], poses=[ctx, query]))`` — whose
         rows go through the same LayerNorm / dense launches as there (on B*N*L rows) and whose attention reads the context's keys and
         values from the cache (ops.attn_prefix).  Queries are independent of each other: a query's rows do not depend on N.
         ``return_confidence`` (with ``codes_only``): (codes, confidence, entropy), the last two fp32 [B,N,t,t] — log p of the generated
-        code (max logit - lse) and the entropy of the token's distribution, from the same LM-head launch (``_lm_score``)."""
+        code (max logit - lse) and the entropy of the token's distribution, from the same LM-head launch (``_lm_score``).
+        ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
+        keyword); consecutive views share an attention group, which costs what its longest member costs."""
         if not isinstance(cache, ContextCache):
             raise TypeError('generate_from_context: a ContextCache from prefill_context expected')
         if return_confidence and not codes_only:
@@ -393,6 +412,7 @@ class MIGT:
         self._check_render_shapes(L)
         d, H, nE = c.d_model, c.n_head, c.n_embeddings
         M = B * N * L
+        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             if return_confidence:
                 return (torch.empty((B, 0, *tshape), dtype=torch.int64, device=dev), torch.empty((B, 0, *tshape), dtype=torch.float32, device=dev),
@@ -401,7 +421,7 @@ class MIGT:
                     else torch.empty((B, 0, *tshape, nE), dtype=torch.float32, device=dev))
         add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
         ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
-        hf = self._query_rows(cache, ids32, add, N)
+        hf = self._query_rows(cache, ids32, add, N, ctx)
         if return_confidence:
             st = self._lm_score(hf, M, want=('idx', 'max_logit', 'lse', 'entropy'))
             return st['idx'].view(B, N, *tshape), (st['max_logit'] - st['lse']).view(B, N, *tshape), st['entropy'].view(B, N, *tshape)
@@ -414,7 +434,7 @@ class MIGT:
             gen = ops.argmax_rows(lg, M, nE)
         return gen.view(B, N, *tshape)
 
-    def score_from_context(self, cache, query_cameras, codes, fused: bool = False):
+    def score_from_context(self, cache, query_cameras, codes, fused: bool = False, n_context=None):
         """How well do photos fit cameras?  ``query_cameras`` fp32 [B,N,7] in the context's (relative, normalised) frame, ``codes`` int
         [B,N,t,t] (one photo per camera) or [B,1,t,t] (one photo per scene against N candidate cameras) -> dict of
             token_log_prob  fp32 [B,N,t,t]   log p(code) under the MASK view at that camera: target logit - lse
@@ -425,7 +445,9 @@ class MIGT:
             accuracy        fp32 [B,N]       share of a view's tokens where the prediction is the photo's code
         Every camera is a MASK view exactly as in ``generate_from_context`` (same pose embedding, same ``_query_rows`` launches); the LM
         head then yields five numbers per row (``_lm_score``: through the logits and the row kernel; ``fused=True``: in the bf16 head's
-        epilogue without the logits, the slower route on the MI355X, kept for A/B runs and tests).  A code outside [0, n_embeddings) has log-probability -inf.  Views are independent: a view's results do not depend on N."""
+        epilogue without the logits, the slower route on the MI355X, kept for A/B runs and tests).  A code outside [0, n_embeddings) has log-probability -inf.  Views are independent: a view's results do not depend on N.
+        ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
+        keyword); consecutive views share an attention group, which costs what its longest member costs."""
         if not isinstance(cache, ContextCache):
             raise TypeError('score_from_context: a ContextCache from prefill_context expected')
         B, tshape = cache.B, cache.tshape
@@ -443,6 +465,7 @@ class MIGT:
             raise ValueError(f'codes int [B={B},N={N} or 1,{",".join(map(str, tshape))}] expected, got {codes.dtype} {tuple(codes.shape)}')
         d = c.d_model
         M = B * N * L
+        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             e4 = lambda dt: torch.empty((B, 0, *tshape), dtype=dt, device=dev)
             e2 = lambda: torch.empty((B, 0), dtype=torch.float32, device=dev)
@@ -451,14 +474,14 @@ class MIGT:
         target = codes.to(torch.int32).expand(B, N, *tshape).reshape(M).contiguous()
         add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
         ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
-        hf = self._query_rows(cache, ids32, add, N)
+        hf = self._query_rows(cache, ids32, add, N, ctx)
         st = self._lm_score(hf, M, target, fused=fused)
         tlp, conf, ll, acc = ops.score_views(st, target, B * N, L)           # log-likelihood: one fp32 chain per view, in token order
         return dict(token_log_prob=tlp.view(B, N, *tshape), log_likelihood=ll.view(B, N), predicted_codes=st['idx'].view(B, N, *tshape),
                     confidence=conf.view(B, N, *tshape), entropy=st['entropy'].view(B, N, *tshape), accuracy=acc.view(B, N))
 
     def sample_from_context(self, cache, query_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                            seed: int = 0, view0: int = 0, return_logits: bool = False):
+                            seed: int = 0, view0: int = 0, return_logits: bool = False, n_context=None):
         """Draw S = ``n_samples`` code maps per query view from the model's distribution: ``query_cameras`` fp32 [B,N,7] in the context's
         (relative, normalised) frame -> dict of
             codes           int64 [B,N,S,t,t]  the draws
@@ -471,7 +494,9 @@ class MIGT:
         kernel (ops.sample_rows: temperature, top-k, top-p and the S Gumbel-max draws).  ``top_k = 1`` gives ``generate_from_context``'s
         codes whatever the seed.  The noise of token l of view n of scene b is keyed by (seed, row_id = (b << 32) | ((view0 + n) L + l),
         sample index), b being the scene's number in the cache's batch: a token's draws do not depend on B, on N or on how the views are chunked (``view0`` = the number of the chunk's
-        first view)."""
+        first view).
+        ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
+        keyword); consecutive views share an attention group, which costs what its longest member costs."""
         if not isinstance(cache, ContextCache):
             raise TypeError('sample_from_context: a ContextCache from prefill_context expected')
         B, tshape = cache.B, cache.tshape
@@ -492,6 +517,7 @@ class MIGT:
             raise ValueError(f'sample_from_context: 0 <= view0 and (view0 + N) * {L} < 2^32 expected, got view0 = {view0}, N = {N}')
         d, nE = c.d_model, c.n_embeddings
         M = B * N * L
+        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             res = dict(codes=torch.empty((B, 0, S, *tshape), dtype=torch.int64, device=dev),
                        token_log_prob=torch.empty((B, 0, S, *tshape), dtype=torch.float32, device=dev),
@@ -502,7 +528,7 @@ class MIGT:
             return res
         add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
         ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
-        hf = self._query_rows(cache, ids32, add, N)
+        hf = self._query_rows(cache, ids32, add, N, ctx)
         lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
         self._lm(hf, M, lg)                                                  # migt.py:417
         row_id = ((torch.arange(B, dtype=torch.int64, device=dev) << 32).view(B, 1)
@@ -517,7 +543,7 @@ class MIGT:
             res['logits'] = lg.view(B, N, *tshape, nE)
         return res
 
-    def localize_from_context(self, cache, codes, return_tokens: bool = False, fused_tail: bool = True):
+    def localize_from_context(self, cache, codes, return_tokens: bool = False, fused_tail: bool = True, n_context=None):
         """Localize N photos per scene against a prefilled context: ``codes`` int [B,N,t,t] (the photos' code maps) -> cameras fp32
         [B,N,7] in the context's (relative, normalised) frame; with ``return_tokens`` a dict(cameras, pose_prediction [B,N,L,7],
         raw [B,N,L,7] — the pose classifier's output before post-processing).  Every photo is a LOC view — ``wte[codes] + wpe +
@@ -526,7 +552,9 @@ class MIGT:
         classifier.  ``fused_tail``: c_proj, the per-token post-processing and the reduction over a view's tokens as one launch
         (ops.pose_tail) where the kernel takes the shape; otherwise, and with ``fused_tail=False``, the GEMM and
         geometry.pose_head_postprocess / reduce_cameras as ``__call__`` and the evaluators run them.  Photos are independent of each
-        other: a photo's result does not depend on N."""
+        other: a photo's result does not depend on N.
+        ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
+        keyword); consecutive views share an attention group, which costs what its longest member costs."""
         if not self.use_localization:
             raise RuntimeError('localize_from_context needs a model with the localization head')
         if not isinstance(cache, ContextCache):
@@ -542,6 +570,7 @@ class MIGT:
         N = codes.shape[1]
         d = c.d_model
         M = B * N * L
+        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             cams = torch.empty((B, 0, 7), dtype=torch.float32, device=dev)
             if not return_tokens:
@@ -550,7 +579,7 @@ class MIGT:
                         raw=torch.empty((B, 0, L, 7), dtype=torch.float32, device=dev))
         add = self._wte[self.localization_token].view(1, d).expand(B * N, d).contiguous()            # migt.py:387-390
         ids32 = codes.reshape(M).to(torch.int32).contiguous()
-        hf = self._query_rows(cache, ids32, add, N)
+        hf = self._query_rows(cache, ids32, add, N, ctx)
         p1 = self._gemm(hf, 'pose_criterion.pose_classifier.c_fc', M, epilogue=ops.EPI_GELU)
         cp = self._dense['pose_criterion.pose_classifier.c_proj']
         if fused_tail and cp.n == 7 and ops.pose_tail_supported(cp.k, L):

@@ -589,19 +589,35 @@ def attn_blockcausal(q, k, v, out, B, H, T, L, ldq, ldk, ldv, ldo, scale=1.0, sk
     return out
 
 
-def attn_prefix(q, k, v, kp, vp, out, B, H, C, N, L, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldo, bf16=False, dh=64):
+def attn_prefix(q, k, v, kp, vp, out, B, H, C, N, L, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldo, bf16=False, dh=64, ctx_len=None):
     """Attention of N independent query views per scene over a cached prefix of C views plus each view's own tile
     (csrc/attention_prefix.hip).  q / k / v: the query rows' thirds of the fused c_attn output, [B*N*L] rows; kp / vp: the cached
     K / V, [C*L] rows per scene, scenes ``prefix_stride`` elements apart.  ``bf16``: the tolerance arm (bf16 or fp32 tensors, one
-    dtype for all five inputs; bf16 or fp32 ``out``); default: the fp32-equivalent arm (fp32 tensors)."""
+    dtype for all five inputs; bf16 or fp32 ``out``); default: the fp32-equivalent arm (fp32 tensors).  ``ctx_len``: None (every view
+    attends to all C cached views: the fixed-C entries, exactly as without the keyword) or an int32 device tensor [B*N], view (b, n)
+    attending to the first ``ctx_len[b*N+n]`` cached views (0 <= length <= C, the caller's to ensure: the kernel clamps) and to itself
+    (vf_attn_prefix_var_*).  A workgroup (4 / 2 consecutive views) costs what its longest member costs."""
     lib = _lib.load()
+    if ctx_len is not None:
+        _chk(ctx_len, torch.int32, 'ctx_len')
+        if ctx_len.numel() != B * N or not ctx_len.is_contiguous():
+            raise ValueError(f'attn_prefix: ctx_len int32 [B*N = {B * N}] contiguous expected, got {tuple(ctx_len.shape)}')
     if bf16:
         o16 = out.dtype == torch.bfloat16
         i16 = q.dtype == torch.bfloat16
         for t in (q, k, v, kp, vp):
             _chk(t, torch.bfloat16 if i16 else torch.float32, 'q/k/v/prefix')
+        if ctx_len is not None:
+            check(lib.vf_attn_prefix_var_bf16(_p(q), _p(k), _p(v), _p(kp), _p(vp), 1 if i16 else 0, _p(out if o16 else _f32(out)),
+                                              1 if o16 else 0, B, H, C, N, L, dh, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldo, _p(ctx_len),
+                                              _stream()), 'vf_attn_prefix_var_bf16')
+            return out
         check(lib.vf_attn_prefix_bf16(_p(q), _p(k), _p(v), _p(kp), _p(vp), 1 if i16 else 0, _p(out if o16 else _f32(out)), 1 if o16 else 0,
                                       B, H, C, N, L, dh, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldo, _stream()), 'vf_attn_prefix_bf16')
+        return out
+    if ctx_len is not None:
+        check(lib.vf_attn_prefix_var_f32eq(_p(_f32(q)), _p(_f32(k)), _p(_f32(v)), _p(_f32(kp)), _p(_f32(vp)), _p(_f32(out)), B, H, C, N, L, dh,
+                                           ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldo, _p(ctx_len), _stream()), 'vf_attn_prefix_var_f32eq')
         return out
     check(lib.vf_attn_prefix_f32eq(_p(_f32(q)), _p(_f32(k)), _p(_f32(v)), _p(_f32(kp)), _p(_f32(vp)), _p(_f32(out)), B, H, C, N, L, dh,
                                    ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldo, _stream()), 'vf_attn_prefix_f32eq')

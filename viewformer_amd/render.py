@@ -9,6 +9,7 @@ and values are computed once (``MIGT.prefill_context``) and each query is a sing
     r = ViewRenderer(transformer_model, codebook_model)
     r.set_context(images=frames_u8, cameras=cams)            # or codes=... (scene_bank.SceneBank.gather)
     out = r.render(query_cameras)                            # out['generated_images'] uint8 [B,N,H,W,3]
+    swp = r.sweep(query_cameras)                             # swp['generated_images'] uint8 [B,N,C+1,H,W,3]: the view from 0, 1, ..., C photos
     est = r.localize(images=photos_u8)                       # est['generated_cameras'] fp32 [B,N,7], the caller's world frame
     fit = r.score(candidate_cameras, images=photo_u8)        # fit['log_likelihood'] fp32 [B,N]: how well the photo fits each camera
     alt = r.sample(query_cameras, n_samples=8, top_p=0.9)    # alt['generated_images'] uint8 [B,N,8,H,W,3]: draws, with their log-likelihood
@@ -21,9 +22,15 @@ Localization uses the same cache: the LOC view of a photo is 
 context and itself, so N photos against C context photographs cost N encodes and N transformer views
 (``MIGT.localize_from_context``) instead of N * (C + 1) of each; one ``set_context`` serves ``render`` and ``localize`` alike.
 
-Not covered here: contexts that change per query (the 7-Scenes pose-refinement loop) and the multi-context ``evaluate_sequence`` path;
-both keep their evaluators.
+Context lengths: the context is block-causal, ``wpe`` indexes the token inside a view and the cameras are relative to
+view 0 camera by camera, so the first c views of a C-view cache ARE the cache of those c views.  ``n_context`` — per scene in
+``set_context`` (a ragged batch padded to C), per scene or per query view in the four methods — makes a query walk only that many prefix
+tiles (``ops.attn_prefix(ctx_len=...)``): ``sweep`` answers "how good is the view from 0, 1, ..., C photos" from one prefill, and
+``evaluate_context_sizes`` is the cached drop-in for ``evaluate_multictx.generate_batch_predictions``.
+
+Not covered here: contexts that change per query (the 7-Scenes pose-refinement loop); it keeps its evaluator.
 """
+import numpy as np
 import torch
 
 from . import geometry
@@ -67,6 +74,43 @@ def plan_view_chunks(n_views: int, n_scenes: int = 1, max_views_per_call: int = 
     return [(a, min(a + cap, n_views)) for a in range(0, n_views, cap)]
 
 
+def plan_context_lengths(n_context, B: int, N: int, C: int, scene_default=None):
+    """Context lengths of N query views per scene, normalised: ``n_context`` — an int, [B] (one length per scene) or [B,N] (one per
+    query view) of integers in [0, C]; host data preferred, a device tensor is brought to the host once — -> int32 array [B,N].
+    ``None`` -> ``scene_default`` ([B], e.g. ``set_context``'s) broadcast the same way, or None without one (today's rectangular path).
+    Floats, bools, values outside [0, C] and other shapes raise ValueError.  Pure: no device, no model."""
+    if n_context is None:
+        n_context = scene_default
+        if n_context is None:
+            return None
+    if isinstance(n_context, torch.Tensor):
+        n_context = n_context.detach().cpu().numpy()
+    a = np.asarray(n_context)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f'n_context: integers expected, got {a.dtype}')
+    if a.ndim == 0:
+        a = np.broadcast_to(a, (B, N))
+    elif a.shape == (B,):
+        a = np.broadcast_to(a.reshape(B, 1), (B, N))
+    elif a.shape != (B, N) or a.ndim != 2:
+        raise ValueError(f'n_context: an int, [B={B}] or [B={B},N={N}] expected, got {a.shape}')
+    if a.size and (a.min() < 0 or a.max() > C):
+        raise ValueError(f'n_context: values in [0, C={C}] expected, got {int(a.min())} ... {int(a.max())}')
+    return np.array(a, dtype=np.int32, order='C')                  # always a copy: the caller's array (or a broadcast view) stays as it is
+
+
+def sweep_layout(N: int, K: int):
+    """The order in which ``ViewRenderer.sweep`` renders N cameras at K context sizes, and the way back: (camera [K*N], size [K*N],
+    inverse [N,K]).  Rendered view j is camera ``camera[j]`` at size number ``size[j]``, SIZE-MAJOR (j = k N + n): consecutive views
+    have equal lengths, so the attention's groups of 4 / 2 consecutive views stay homogeneous.  ``inverse[n, k]`` = the rendered index
+    of (camera n, size k): ``x[:, inverse.reshape(-1)].view(B, N, K, ...)`` is the result per camera.  Pure."""
+    if N < 0 or K < 0:
+        raise ValueError(f'sweep_layout: N >= 0 and K >= 0 expected, got {N} and {K}')
+    j = np.arange(K * N, dtype=np.int64)
+    inverse = (np.arange(K, dtype=np.int64).reshape(1, K) * N + np.arange(N, dtype=np.int64).reshape(N, 1))
+    return (j % N if N else j), (j // N if N else j), inverse
+
+
 class ViewRenderer:
     def __init__(self, transformer_model, codebook_model):
         self.transformer = transformer_model
@@ -74,13 +118,17 @@ class ViewRenderer:
         self.cache = None
         self.transform = None
         self.context_codes = None
+        self.n_context = None              # set_context(n_context=...): valid context views per scene, int32 [B] (host), the methods' default
         self.fused_score = None            # score: None = MIGT.score_from_context's default route, True / False = the fused LM head / through the logits
         self.fused_tail = None             # localize: None = MIGT.localize_from_context's default tail, True / False = the fused / unfused one
 
-    def set_context(self, images=None, cameras=None, codes=None):
+    def set_context(self, images=None, cameras=None, codes=None, n_context=None):
         """``images`` uint8 [B,C,H,W,3] (host or device; resized for the encoder as the evaluators do) or ``codes`` int [B,C,t,t]
         (already encoded, e.g. ``SceneBank.gather``), and ``cameras`` [B,C,7] in the caller's world frame.  Encodes once, prefills the
-        transformer's key / value cache once."""
+        transformer's key / value cache once.  ``n_context``: [B] (or an int), the number of valid context views per scene in [1, C],
+        for a ragged batch padded to C: scene b's queries see its first ``n_context[b]`` views only (the default of ``render``,
+        ``sample``, ``score``, ``localize`` and ``sweep``).  Padding views must hold valid code ids (or images) and finite cameras; they
+        are computed by the prefill and never read by a query.  View 0 is valid in every scene, so the poses' frame is each scene's own."""
         tm, cm = self.transformer, self.codebook
         dev = cm.device
         if cameras is None or (images is None) == (codes is None):
@@ -90,6 +138,13 @@ class ViewRenderer:
             raise ValueError(f'set_context: cameras [B,C,7] expected, got {tuple(cameras.shape)}')
         B, C = cameras.shape[:2]
         t = tm.config.token_image_size
+        if n_context is not None:
+            a = np.asarray(n_context.detach().cpu().numpy() if isinstance(n_context, torch.Tensor) else n_context)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape != (B,)):
+                raise ValueError(f'set_context: n_context an int or [B={B}] expected, got {a.shape}')
+            n_context = plan_context_lengths(a, B, 1, C)[:, 0].copy()
+            if n_context.size and n_context.min() < 1:
+                raise ValueError(f'set_context: n_context in [1, C={C}] expected (a scene has at least one context view), got {int(n_context.min())}')
         poses, transform = context_poses(cameras, tm.config.augment_poses)
         if codes is None:
             images = torch.as_tensor(images).to(dev)
@@ -102,7 +157,7 @@ class ViewRenderer:
                 raise ValueError(f'set_context: codes {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
         codes = codes.to(torch.int32).view(B, C, t, t)
         self.cache = tm.prefill_context(codes, poses)
-        self.transform, self.context_codes = transform, codes
+        self.transform, self.context_codes, self.n_context = transform, codes, n_context
         return self
 
     def _decode(self, flat, keep_decoded: bool = False):
@@ -129,12 +184,22 @@ class ViewRenderer:
         dec = torch.cat(decs) if len(decs) > 1 else (decs[0] if decs else torch.empty((0, *img.shape[1:]), dtype=torch.float32, device=dev))
         return img, dec
 
-    def render(self, query_cameras, max_views_per_call: int = None, return_codes: bool = False, return_confidence: bool = False):
+    def _lengths(self, n_context, N):
+        """the methods' ``n_context`` (an int, [B] or [B,N]; None: ``set_context``'s per-scene default) -> int32 [B,N] or None"""
+        if n_context is None and self.n_context is None:
+            return None                                                  # the rectangular path: nothing is asked of the cache
+        return plan_context_lengths(n_context, self.cache.B, N, self.cache.C, scene_default=self.n_context)
+
+    def render(self, query_cameras, max_views_per_call: int = None, return_codes: bool = False, return_confidence: bool = False,
+               n_context=None):
         """``query_cameras`` [B,N,7] in the caller's world frame (the context's) -> dict(generated_images uint8 [B,N,H,W,3]); with
         ``return_codes`` also generated_codes int64 [B,N,t,t], logits fp32 [B,N,t,t,n_embeddings] and decoded (the decoder's fp32
         output [B,N,H,W,3]).  N is walked in chunks of whole views (``plan_view_chunks``); a view's result does not depend on the
         chunking.  With ``return_confidence`` also confidence and entropy, fp32 [B,N,t,t] each: log p of every generated token and the
-        entropy of its distribution (which of a view's tokens the model was guessing), from the LM-head launch that generates the codes."""
+        entropy of its distribution (which of a view's tokens the model was guessing), from the LM-head launch that generates the codes.
+        ``n_context``: an int, [B] or [B,N] in [0, C] — the number of leading context views each query sees, overriding
+        ``set_context``'s per-scene default; sliced per chunk with the views.  4 (bf16) / 2 (f32) consecutive views share an attention
+        workgroup, which costs what its longest member costs: keep equal lengths together (``sweep`` does)."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.render: set_context() first')
         tm, cm = self.transformer, self.codebook
@@ -147,20 +212,22 @@ class ViewRenderer:
         t = tm.config.token_image_size
         nE = tm.config.n_embeddings
         poses = query_poses(query_cameras, self.transform)
+        lens = self._lengths(n_context, N)
         gen, lgs, conf, ent = [], [], [], []
         for a, b in plan_view_chunks(N, B, max_views_per_call):
+            kw = {} if lens is None else dict(n_context=lens[:, a:b])
             if return_confidence and not return_codes:
-                g, cf, en = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True, return_confidence=True)
+                g, cf, en = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True, return_confidence=True, **kw)
                 gen.append(g); conf.append(cf); ent.append(en)
             elif return_codes:
-                lg = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=False)
+                lg = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=False, **kw)
                 lgs.append(lg)
                 gen.append(ops.argmax_rows(lg.view(-1, nE), B * (b - a) * t * t, nE).view(B, b - a, t, t))   # ties -> lowest index
                 if return_confidence:                      # the logits exist already: the row kernel on them
                     st = ops.logits_score(lg.view(-1, nE), B * (b - a) * t * t, nE, want=('max_logit', 'lse', 'entropy'))
                     conf.append((st['max_logit'] - st['lse']).view(B, b - a, t, t)); ent.append(st['entropy'].view(B, b - a, t, t))
             else:
-                gen.append(tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True))
+                gen.append(tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True, **kw))
         codes = torch.cat(gen, 1) if gen else torch.empty((B, 0, t, t), dtype=torch.int64, device=dev)
         img, dec = self._decode(codes.reshape(B * N, t, t), keep_decoded=return_codes)
         res = dict(generated_images=img.view(B, N, *img.shape[1:]))
@@ -174,7 +241,7 @@ class ViewRenderer:
         return res
 
     def sample(self, query_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-               max_views_per_call: int = None, return_codes: bool = False):
+               max_views_per_call: int = None, return_codes: bool = False, n_context=None):
         """Draw ``n_samples`` = S plausible views per camera: ``query_cameras`` [B,N,7] in the caller's world frame (the context's) ->
         dict(generated_images uint8 [B,N,S,H,W,3], log_likelihood fp32 [B,N,S]: the log-probability of each drawn code map under the
         distribution it was drawn from); with ``return_codes`` also generated_codes int64 [B,N,S,t,t], token_log_prob fp32 [B,N,S,t,t]
@@ -183,7 +250,8 @@ class ViewRenderer:
         (seed, the scene's NUMBER b in this context's batch, view number, token, sample number) and not on the batch size, on N or on the
         chunking — N is walked in chunks of whole views (``plan_view_chunks``) and a view's result does not depend on it.  Because the
         noise is keyed by b, a scene set as the context alone (b = 0) and the same scene at b = 1 of a batch get DIFFERENT draws for one
-        seed (same distribution, same kept sets, same ``top_k = 1`` result); only scene 0 of a batch reproduces its stand-alone draws."""
+        seed (same distribution, same kept sets, same ``top_k = 1`` result); only scene 0 of a batch reproduces its stand-alone draws.
+        ``n_context``: as ``render``'s."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.sample: set_context() first')
         tm, cm = self.transformer, self.codebook
@@ -197,7 +265,10 @@ class ViewRenderer:
         t = tm.config.token_image_size
         poses = query_poses(query_cameras, self.transform)
         kw = dict(n_samples=S, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
-        parts = [tm.sample_from_context(self.cache, poses[:, a:b], view0=a, **kw) for a, b in plan_view_chunks(N, B, max_views_per_call)]
+        lens = self._lengths(n_context, N)
+        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
+        parts = [tm.sample_from_context(self.cache, poses[:, a:b], view0=a, **kw, **lkw(a, b))
+                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
         if not parts:
             parts = [tm.sample_from_context(self.cache, poses, **kw)]               # N = 0: empty tensors of the right shapes
         out = {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
@@ -207,13 +278,14 @@ class ViewRenderer:
             res.update(generated_codes=out['codes'], token_log_prob=out['token_log_prob'], kept=out['kept'])
         return res
 
-    def score(self, query_cameras, images=None, codes=None, max_views_per_call: int = None):
+    def score(self, query_cameras, images=None, codes=None, max_views_per_call: int = None, n_context=None):
         """How well do photos fit cameras?  ``query_cameras`` [B,N,7] in the caller's world frame (the context's) and ``images`` uint8
         [B,N,H,W,3] or [B,1,H,W,3] (host or device; resized for the encoder as the evaluators do, each photo encoded once) or ``codes``
         int [B,N,t,t] or [B,1,t,t] (already encoded) -> ``MIGT.score_from_context``'s dict: token_log_prob, predicted_codes, confidence,
         entropy [B,N,t,t]; log_likelihood, accuracy [B,N].  One photo per scene (a view axis of 1) is scored against all N cameras:
         ranking candidate poses.  N is walked in chunks of whole views (``plan_view_chunks``); a view's result does not depend on the
-        chunking.  ``self.fused_score`` (None = the model's default route, True / False = the fused head / through the logits) is for A/B runs."""
+        chunking.  ``self.fused_score`` (None = the model's default route, True / False = the fused head / through the logits) is for A/B runs.
+        ``n_context``: as ``render``'s."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.score: set_context() first')
         if (images is None) == (codes is None):
@@ -243,18 +315,20 @@ class ViewRenderer:
         poses = query_poses(query_cameras, self.transform)
         kw = {} if self.fused_score is None else dict(fused=bool(self.fused_score))
         one = P == 1 and N != 1
-        parts = [tm.score_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **kw)
+        lens = self._lengths(n_context, N)
+        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
+        parts = [tm.score_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **kw, **lkw(a, b))
                  for a, b in plan_view_chunks(N, B, max_views_per_call)]
         if not parts:
             parts = [tm.score_from_context(self.cache, poses, codes[:, :0], **kw)]      # N = 0: empty tensors of the right shapes
         return {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
 
-    def localize(self, images=None, codes=None, max_views_per_call: int = None, return_tokens: bool = False):
+    def localize(self, images=None, codes=None, max_views_per_call: int = None, return_tokens: bool = False, n_context=None):
         """Estimate the cameras of N photos per scene against the context: ``images`` uint8 [B,N,H,W,3] (host or device; resized for
         the encoder as the evaluators do, each photo encoded once) or ``codes`` int [B,N,t,t] (already encoded, e.g.
         ``SceneBank.gather``) -> dict(generated_cameras fp32 [B,N,7]) in the caller's world frame (the context cameras'); with
         ``return_tokens`` also codes int32 [B,N,t,t], pose_prediction [B,N,L,7] (the per-token poses in the context's frame) and raw
-        [B,N,L,7].  N is walked in chunks of whole views (``plan_view_chunks``)."""
+        [B,N,L,7].  N is walked in chunks of whole views (``plan_view_chunks``).  ``n_context``: as ``render``'s."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.localize: set_context() first')
         if (images is None) == (codes is None):
@@ -279,7 +353,9 @@ class ViewRenderer:
             N = codes.numel() // (B * t * t)
         codes = codes.to(torch.int32).view(B, N, t, t)
         kw = dict(return_tokens=return_tokens, **({} if self.fused_tail is None else dict(fused_tail=bool(self.fused_tail))))
-        parts = [tm.localize_from_context(self.cache, codes[:, a:b], **kw) for a, b in plan_view_chunks(N, B, max_views_per_call)]
+        lens = self._lengths(n_context, N)
+        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
+        parts = [tm.localize_from_context(self.cache, codes[:, a:b], **kw, **lkw(a, b)) for a, b in plan_view_chunks(N, B, max_views_per_call)]
         if not parts:
             parts = [tm.localize_from_context(self.cache, codes, **kw)]             # N = 0: empty tensors of the right shapes
         cat = lambda ts: torch.cat(ts, 1) if len(ts) > 1 else ts[0]
@@ -291,12 +367,78 @@ class ViewRenderer:
             res.update(codes=codes, pose_prediction=cat([p['pose_prediction'] for p in parts]), raw=cat([p['raw'] for p in parts]))
         return res
 
+    def sweep(self, query_cameras, sizes=None, max_views_per_call: int = None, return_codes: bool = False):
+        """The view at every camera from every context size: ``query_cameras`` [B,N,7] in the caller's world frame, ``sizes`` K integers
+        in [0, C] (default 0 ... C; size 0 = no context photo at all) -> dict(generated_images uint8 [B,N,K,H,W,3], sizes int32 [K]);
+        with ``return_codes`` also generated_codes int64 [B,N,K,t,t] and logits fp32 [B,N,K,t,t,n_embeddings].  ONE ``render`` over
+        K N views laid out size-major (``sweep_layout``), from the one prefill: no context is encoded or prefilled per size.  After
+        ``set_context(n_context=...)`` a size above a scene's number of valid views is that number (its padding is never read)."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.sweep: set_context() first')
+        B, C = self.cache.B, self.cache.C
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(self.codebook.device)
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
+            raise ValueError(f'sweep: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        sz = np.arange(C + 1) if sizes is None else np.asarray(sizes.detach().cpu().numpy() if isinstance(sizes, torch.Tensor) else sizes)
+        if sz.ndim != 1 or sz.dtype == np.bool_ or not np.issubdtype(sz.dtype, np.integer) or (sz.size and (sz.min() < 0 or sz.max() > C)):
+            raise ValueError(f'sweep: sizes, a list of integers in [0, C={C}], expected, got {sizes}')
+        sz = sz.astype(np.int32)
+        K = sz.shape[0]
+        cam, size, inverse = sweep_layout(N, K)
+        lens = np.broadcast_to(sz[size].reshape(1, K * N), (B, K * N))
+        if self.n_context is not None:
+            lens = np.minimum(lens, self.n_context.reshape(B, 1))
+        out = self.render(query_cameras[:, torch.from_numpy(cam).to(query_cameras.device)], max_views_per_call=max_views_per_call,
+                          return_codes=return_codes, n_context=np.ascontiguousarray(lens, dtype=np.int32))
+        back = torch.from_numpy(inverse.reshape(-1)).to(query_cameras.device)
+        per_camera = lambda x: x[:, back].view(B, N, K, *x.shape[2:])
+        res = dict(generated_images=per_camera(out['generated_images']), sizes=torch.from_numpy(sz))
+        if return_codes:
+            res.update(generated_codes=per_camera(out['generated_codes']), logits=per_camera(out['logits']))
+        return res
+
+
+def evaluate_context_sizes(transformer_model, codebook_model, images, cameras):
+    """``evaluate_multictx.generate_batch_predictions`` from ONE cached context: ``images`` uint8 [B,S,H,W,3], ``cameras`` [B,S,7] -> the
+    same keys and shapes — ground_truth_images, generated_images [B,S,H,W,3], ground_truth_cameras, generated_cameras [B,S,7],
+    generated_codes [B,S,t,t], codes [B,S,t,t] — entry i being the last frame's view / pose from the first i frames as context.  All S
+    frames are encoded once (as there); the S-1 context frames are prefilled once, the target camera is swept over the sizes 0 ... S-1
+    and the target's code map is localized against the same sizes.  S = 1 leaves no context view: ValueError."""
+    dev = codebook_model.device
+    images = torch.as_tensor(images).to(dev)
+    cameras = torch.as_tensor(cameras, dtype=torch.float32).to(dev)
+    if images.dim() != 5 or cameras.dim() != 3 or cameras.shape[-1] != 7 or tuple(images.shape[:2]) != tuple(cameras.shape[:2]):
+        raise ValueError(f'evaluate_context_sizes: images [B,S,H,W,3] and cameras [B,S,7] expected, got {tuple(images.shape)} and '
+                         f'{tuple(cameras.shape)}')
+    B, S = images.shape[:2]
+    if S < 2:
+        raise ValueError('evaluate_context_sizes: S >= 2 expected (S - 1 context views and the target)')
+    t = transformer_model.config.token_image_size
+    codes = codebook_model.encode(_frames_for_encode(images, codebook_model.config.image_size))[-1].to(torch.int32).view(B, S, t, t)
+    r = ViewRenderer(transformer_model, codebook_model).set_context(codes=codes[:, :-1], cameras=cameras[:, :-1])
+    sizes = np.arange(S, dtype=np.int32)
+    swp = r.sweep(cameras[:, -1:], sizes=sizes, return_codes=True)
+    loc = r.localize(codes=codes[:, -1:].expand(B, S, t, t).contiguous(), n_context=sizes.reshape(1, S).repeat(B, 0))
+    return dict(ground_truth_images=images[:, -1], generated_images=swp['generated_images'][:, 0],
+                ground_truth_cameras=cameras[:, -1], generated_cameras=loc['generated_cameras'],
+                generated_codes=swp['generated_codes'][:, 0], codes=codes)
+
 
 def render_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.render``'s
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``max_views_per_call``, ``return_codes``."""
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
     return r.render(query_cameras, **kw)
+
+
+def sweep_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.sweep``'s
+    dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``n_context`` (valid context views per scene),
+    ``sizes``, ``max_views_per_call``, ``return_codes``."""
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None),
+                                                                    n_context=kw.pop('n_context', None))
+    return r.sweep(query_cameras, **kw)
 
 
 def sample_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
