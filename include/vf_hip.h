@@ -307,6 +307,19 @@ int vf_attn_prefix_var_bf16(const void* q, const void* k, const void* v, const v
 int vf_attn_prefix_var_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
                              int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                              int ldo, const int32_t* ctx_len, void* stream);
+/* Append the keys and values of K new views per scene to a context cache with room (csrc/kv_append.hip): qkv = the fused c_attn output of
+ * the new views, rows [B*K*L][ld_src], thirds (V, Q, K); for scene b and new view j the V third (columns [0, d)) and the K third (columns
+ * [2d, 3d)) of the view's L rows are copied to rows (pos[b] + j) L ... of scene b of `cache` (leading dimension ld_dst, scenes cache_stride
+ * elements apart, `capacity` views of room per scene).  pos: DEVICE pointer to [B] int32, each scene's own current length (ragged batches,
+ * no host round trip).  One launch for all scenes and views; elem_bytes 2 (bf16) or 4 (fp32); the copy is bit-exact.  Footprint: reads the
+ * two thirds of the B*K*L rows and pos; writes exactly the two thirds of the rows named above — the destination's Q third, every other row
+ * and every other scene keep their bits.  A view whose pos[b] + j falls outside [0, capacity) is not written (the kernel clamps as the
+ * attention does; the host never asks for it).  NULL or not 16-byte aligned qkv / cache, NULL pos, elem_bytes not in {2, 4}, a negative size,
+ * ld_* < 3 d, d / ld_* / cache_stride times elem_bytes not a multiple of 16, or (B > 1) a cache_stride below one scene's extent:
+ * VF_ERR_BAD_ARG; B K or the 16-byte chunks of one view (L d elem_bytes / 8) above 2^31 - 1: VF_ERR_UNSUPPORTED; both before any launch.
+ * B, K, L, d or capacity == 0: no-op, VF_OK. */
+int vf_kv_append(const void* qkv, void* cache, int elem_bytes, int B, int K, int L, int d, int ld_src, int ld_dst, int64_t cache_stride,
+                 int capacity, const int32_t* pos, void* stream);
 /* Single-head spatial self-attention of the VQGAN AttnBlock, fused (csrc/attn_spatial.hip): replaces the core of AttnBlock.forward
  * (vqgan_th.py:124-141) — scores = q^T k * scale, softmax over the keys, h = v . p^T — per image of HW tokens x C channels, from the
  * fused q|k|v projection qkv [n_img * HW][ld] (q at column 0, k at C, v at 2C); out [n_img * HW][ldo].  Exact fp32

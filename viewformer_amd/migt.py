@@ -32,17 +32,39 @@ class _Dense:
 
 class ContextCache:
     """Keys and values of C context views in every layer (MIGT.prefill_context): ``kv[i]`` is layer i's fused c_attn output
-    [B*C*L, 3*d_model] with thirds (V, Q, K).  Valid for the model object, weights, arithmetic arm and device that made it."""
-    __slots__ = ('kv', 'B', 'C', 'tshape', 'device', 'arm', 'act16', 'qkv16', '_owner', '_weights')
+    [B*capacity*L, 3*d_model] with thirds (V, Q, K).  Valid for the model object, weights, arithmetic arm and device that made it.
+    ``capacity`` >= C views of room per scene (``prefill_context(capacity=...)``, grown by ``append_to_context``); ``C`` = the number of
+    filled views, the maximum over scenes; ``lengths``: the filled views per scene, host int32 [B], or None for "all C"."""
+    __slots__ = ('kv', 'B', 'C', 'tshape', 'device', 'arm', 'act16', 'qkv16', '_owner', '_weights', 'capacity', 'lengths')
 
-    def __init__(self, model, kv, B, C, tshape):
+    def __init__(self, model, kv, B, C, tshape, capacity=None, lengths=None):
         import weakref
         self.kv, self.B, self.C, self.tshape = kv, B, C, tuple(tshape)
+        self.capacity = C if capacity is None else int(capacity)
+        self.lengths = None if lengths is None else np.array(lengths, dtype=np.int32).reshape(B)
         self.device = model.device
         self.arm = (model.precision, model.dense_arith, model.attention)
         self.act16, self.qkv16 = model._act_dtypes()
         self._owner = weakref.ref(model)
         self._weights = model._weights_version
+
+    def filled(self):
+        """the filled views per scene, int32 [B] (host; a copy)"""
+        return np.full(self.B, self.C, dtype=np.int32) if self.lengths is None else self.lengths.copy()
+
+    def ragged(self):
+        """True where the fixed-C attention entry would read unfilled rows: the cache has slack, or lengths of its own"""
+        return self.capacity != self.C or self.lengths is not None
+
+    def alias(self):
+        """A second ContextCache on the SAME buffers with lengths of its own: what is appended through it lies beyond this cache's lengths
+        (and moves to new buffers, leaving these, once the capacity is exceeded)."""
+        c = object.__new__(ContextCache)
+        for s in self.__slots__:
+            setattr(c, s, getattr(self, s))
+        c.kv = list(self.kv)
+        c.lengths = None if self.lengths is None else self.lengths.copy()
+        return c
 
     def check(self, model):
         if self._owner() is not model or self._weights != model._weights_version:
@@ -326,62 +348,108 @@ class MIGT:
             raise ops._lib.VfError(f'prefix-cache attention supports head dim 64 and 64-token views only (got head dim '
                                    f'{c.d_model // c.n_head}, {L} tokens)')
 
-    def prefill_context(self, codes, cameras):
+    def prefill_context(self, codes, cameras, capacity=None):
         """Run the C context views once and keep every layer's keys and values: ``codes`` int [B,C,t,t], ``cameras`` fp32 [B,C,7]
         (relative + normalised) -> ContextCache for ``generate_from_context``.  Block-causal attention never shows a context view the
         target, ``wpe`` indexes the token inside a view and the poses are relative to view 0, so the context's hidden states — and each
         layer's K / V for them — do not depend on the query.  The cache IS each layer's fused c_attn output (thirds V, Q, K; the Q
-        third is not read again): no copy, dtype as the arm's ``qkv``."""
+        third is not read again): no copy, dtype as the arm's ``qkv``.
+        ``capacity`` >= C: room for that many views per scene and layer ([B*capacity*L, 3d], scenes capacity*L*3d apart), the prefilled
+        views put there by ``ops.kv_append`` at position 0 — for ``append_to_context`` / ``rollout_from_context``, which otherwise
+        reallocate at their first call.  Without it: the buffers and launches above, nothing else."""
         codes = torch.as_tensor(codes).to(self.device)
         cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.device)
         if codes.dim() < 3 or cameras.shape[:2] != codes.shape[:2] or cameras.shape[-1] != 7 or codes.shape[1] < 1:
             raise ValueError(f'prefill_context: codes [B,C,t,t] and cameras [B,C,7] expected, got {tuple(codes.shape)} and {tuple(cameras.shape)}')
         B, C = codes.shape[:2]
+        if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or int(capacity) < C):
+            raise ValueError(f'prefill_context: capacity, an integer >= C = {C}, expected, got {capacity}')
         tshape = tuple(codes.shape[2:])
         L = int(np.prod(tshape))
         self._check_render_shapes(L)
         kv = []
         self._blocks(codes, self._pose_embed(cameras), B, C, L, kv_sink=kv)
-        return ContextCache(self, kv, B, C, tshape)
+        cache = ContextCache(self, kv, B, C, tshape)
+        if capacity is not None and int(capacity) > C:                     # (capacity = C is the tight cache: nothing to move)
+            self._reallocate(cache, int(capacity))
+        return cache
+
+    def _reallocate(self, cache, capacity):
+        """new buffers of ``capacity`` views per scene inside the same ContextCache: every layer's cached views (the V and K thirds of all
+        ``cache.capacity`` views of every scene) copied bit for bit by one ``ops.kv_append`` at position 0"""
+        d, L = self.config.d_model, int(np.prod(cache.tshape))
+        B, old = cache.B, cache.capacity
+        pos0 = torch.zeros(B, dtype=torch.int32, device=self.device)
+        for i, src in enumerate(cache.kv):
+            dst = torch.empty((B * capacity * L, 3 * d), dtype=src.dtype, device=self.device)
+            ops.kv_append(src, dst, B, old, L, d, 3 * d, 3 * d, capacity * L * 3 * d, capacity, pos0)
+            cache.kv[i] = dst
+        cache.capacity = capacity
 
     def _context_lengths(self, cache, n_context, N):
-        """``n_context`` of the four ``*_from_context`` methods -> int32 device tensor [B*N] for ``_query_rows``, or None (None in:
-        every view sees all C cached views, the path and the launches without the keyword).  An int, [B] (one length per scene) or
-        [B,N] (one per query view) of integers in [0, cache.C]: the view sees that many leading context views and itself, which is the
-        model's answer for that context (0: no context at all).  Host data preferred (a device tensor is brought to the host once, to
-        validate it); anything else: ValueError, before any launch.  A group of 4 (bf16) / 2 (f32) consecutive views costs what its
-        longest member costs, and rows are not reordered here."""
-        if n_context is None:
-            return None
+        """``n_context`` of the four ``*_from_context`` methods -> int32 device tensor [B*N] for ``_query_rows``, or None (None in, on a
+        cache without slack and without lengths of its own: every view sees all C cached views, the path and the launches without the
+        keyword; a cache with slack or lengths always takes the length route, and its default lengths are its own: the fixed-C entry
+        would read unfilled rows).  An int, [B] (one length per scene) or [B,N] (one per query view) of integers in [0, the filled length
+        of the scene]: the view sees that many leading context views and itself, which is the model's answer for that context (0: no
+        context at all).  Host data preferred (a device tensor is brought to the host once, to validate it); anything else: ValueError,
+        before any launch.  A group of 4 (bf16) / 2 (f32) consecutive views costs what its longest member costs, and rows are not
+        reordered here."""
         from .render import plan_context_lengths
-        plan = plan_context_lengths(n_context, cache.B, N, cache.C)
+        if n_context is None:
+            if not cache.ragged():
+                return None
+            plan = plan_context_lengths(cache.filled(), cache.B, N, cache.C)
+        else:
+            plan = plan_context_lengths(n_context, cache.B, N, cache.C)
+            if cache.lengths is not None and plan.size and (plan > cache.lengths.reshape(cache.B, 1)).any():
+                raise ValueError(f'n_context: at most the filled views of each scene ({cache.lengths.tolist()}) expected, got {plan.max(1).tolist()}')
         return torch.from_numpy(plan.reshape(-1)).to(self.device)
 
-    def _query_rows(self, cache, ids32, add, N, n_context=None):
+    def _query_rows(self, cache, ids32, add, N, n_context=None, append_at=None, tail='all'):
         """The per-layer loop over the rows of N query views per scene of ``cache``: ``ids32`` int32 [B*N*L] token ids, ``add`` fp32
         [B*N, d] (a pose embedding or the LOC row per view) -> ln_f hidden states [B*N*L, d].  Each view attends to the cached context
         and to itself (ops.attn_prefix); its rows go through the LayerNorm / dense launches of the full pass.  ``n_context``: None, or an
         int32 device tensor [B*N] (``_context_lengths``): view (b, n) attends to the first ``n_context[b*N+n]`` cached views only — the
         model's answer for a context of that many views, since the first c views of a C-view cache are the cache of those c views.
         Rows are not reordered: the attention's workgroups take 4 (bf16) / 2 (f32) consecutive views, and a group costs what its
-        longest member costs."""
+        longest member costs.
+        ``append_at``: None, or an int32 device tensor [B]: in every layer, after c_attn, the keys and values of view n of scene b are put
+        into the cache's view ``append_at[b] + n`` (ops.kv_append) BEFORE the attention, so that with ``n_context[b*N+n] = append_at[b] + n``
+        view n attends to the old context, to the views 0 ... n-1 of this pass and to itself: block-causal attention, same kernel.
+        ``tail``: 'all' (the hidden states of every row), a view number n (the last block's projection, MLP and ln_f on that view's
+        rows only -> [B*L, d]; the rows that are returned keep their bits) or None (nothing is returned: the last block ends once its
+        keys and values are in the cache)."""
         c, dev = self.config, self.device
-        B, C = cache.B, cache.C
+        B, C = cache.B, cache.capacity                                       # the attention's C is the room: lengths say what is filled
         L = int(np.prod(cache.tshape))
         d, H, nE = c.d_model, c.n_head, c.n_embeddings
         M = B * N * L
+        if append_at is not None and n_context is None:
+            raise ValueError('_query_rows: appended views carry their context lengths')
         h = ops.embed_sum(ids32, self._wte, self._wpe, add, B * N, L, d, nE + 2)           # migt.py:392
         act16, qkv16 = cache.act16, cache.qkv16
         att = torch.empty((M, d), dtype=torch.bfloat16 if act16 else torch.float32, device=dev)
         qkv = torch.empty((M, 3 * d), dtype=torch.bfloat16 if qkv16 else torch.float32, device=dev)
         for i in range(c.n_layer):                                           # Block.call on the query rows, migt.py:230-238
             p = f'h.{i}'
+            last = i == c.n_layer - 1
             a = ops.layernorm(h, *self._ln[p + '.ln_1'], M, d, out_bf16=act16)
             self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
-            ckv = cache.kv[i]                                                # [B*C*L, 3d], thirds (V, Q, K)
+            ckv = cache.kv[i]                                                # [B*capacity*L, 3d], thirds (V, Q, K)
+            if append_at is not None:
+                ops.kv_append(qkv, ckv, B, N, L, d, 3 * d, 3 * d, C * L * 3 * d, C, append_at)
+            if last and tail is None:
+                return None                                                  # the last block's other launches feed nothing: the keys and values are in
             ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
                             3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
-            h = self._gemm(att, p + '.attn.c_proj', M, res=h)
+            att_i = att
+            if last and tail != 'all' and N > 1:
+                # the last block: only the returned view's rows go on (as _blocks' tail_views: the other views' rows feed nothing)
+                M = B * L
+                att_i = att.view(B, N, L, d)[:, tail].reshape(M, d)
+                h = h.view(B, N, L, d)[:, tail].reshape(M, d)
+            h = self._gemm(att_i, p + '.attn.c_proj', M, res=h)
             m = ops.layernorm(h, *self._ln[p + '.ln_2'], M, d, out_bf16=act16)
             f = self._gemm(m, p + '.mlp.c_fc', M, epilogue=ops.EPI_GELU, out_bf16=act16)
             h = self._gemm(f, p + '.mlp.c_proj', M, res=h)
@@ -593,6 +661,142 @@ class MIGT:
         if not return_tokens:
             return cams
         return dict(cameras=cams, pose_prediction=tokens.view(B, N, L, 7), raw=raw.view(B, N, L, 7))
+
+    # ------------------------------------------------------------------ a context that grows: appended views, roll-outs along a path
+    def _reserve(self, cache, needed):
+        """room for ``needed`` views per scene: beyond the capacity, new buffers of max(2 capacity, needed) views (render.plan_capacity)"""
+        from .render import plan_capacity
+        if needed > cache.capacity:
+            self._reallocate(cache, plan_capacity(cache.capacity, needed))
+
+    def _grown(self, cache, lengths, K):
+        if cache.lengths is None:
+            cache.C += K
+        else:
+            cache.lengths = (lengths + K).astype(np.int32)
+            cache.C = int(cache.lengths.max())
+
+    def _check_growing(self, cache, cameras, what, name):
+        """the refusals ``append_to_context`` and ``rollout_from_context`` share, before any launch -> (cameras on the device, L)"""
+        if not isinstance(cache, ContextCache):
+            raise TypeError(f'{what}: a ContextCache from prefill_context expected')
+        L = int(np.prod(cache.tshape))
+        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
+        cache.check(self)
+        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.device)
+        if cameras.dim() != 3 or cameras.shape[0] != cache.B or cameras.shape[2] != 7:
+            raise ValueError(f'{what}: {name} [B={cache.B},.,7] expected for this cache, got {tuple(cameras.shape)}')
+        return cameras, L
+
+    def append_to_context(self, cache, codes, cameras):
+        """Grow a context in place by K views per scene: ``codes`` int [B,K,t,t], ``cameras`` fp32 [B,K,7] in the context's (relative,
+        normalised) frame -> the same ContextCache, K views longer in every scene.  ONE pass over the B*K*L new rows: a context view's own
+        embedding (wte[codes] + wpe + pose embedding), and in every layer c_attn, ``ops.kv_append`` at each scene's own length, then
+        ``ops.attn_prefix`` with ``ctx_len = length_b + j`` for new view j — which therefore attends to the old context, to the new views
+        0 ... j-1 (in the cache at this layer already) and to itself: block-causal attention.  The first c views of a cache are the cache
+        of those c views, so no earlier view is touched, and the grown cache holds what ``prefill_context`` of all views would within the
+        arm's own error (the same row launches; the prefill's attention is the block-causal kernel, a new view's the prefix kernel).
+        K views at once and one by one give the same bits where the dense layers take one kernel for both row counts.  Beyond the capacity the cache moves to
+        buffers of max(2 capacity, needed) views, inside the same object.  Foreign caches, the fp8 arm and wrong shapes are refused
+        before any launch."""
+        cameras, L = self._check_growing(cache, cameras, 'append_to_context', 'cameras')
+        dev, d, B, tshape = self.device, self.config.d_model, cache.B, cache.tshape
+        codes = torch.as_tensor(codes).to(dev)
+        if (codes.dim() != 2 + len(tshape) or codes.shape[0] != B or tuple(codes.shape[2:]) != tshape or codes.dtype.is_floating_point
+                or codes.dtype == torch.bool or cameras.shape[1] != codes.shape[1]):
+            raise ValueError(f'append_to_context: codes int [B={B},K,{",".join(map(str, tshape))}] and cameras [B,K,7] expected, got {codes.dtype} '
+                             f'{tuple(codes.shape)} and {tuple(cameras.shape)}')
+        K = codes.shape[1]
+        if K == 0:
+            return cache
+        lengths = cache.filled()
+        self._reserve(cache, int(lengths.max()) + K)
+        pos = torch.from_numpy(lengths).to(dev)
+        ctx = torch.from_numpy((lengths.reshape(B, 1) + np.arange(K, dtype=np.int32).reshape(1, K)).astype(np.int32).reshape(-1)).to(dev)
+        add = self._pose_embed(cameras).contiguous().view(B * K, d)
+        ids32 = codes.reshape(B * K * L).to(torch.int32).contiguous()
+        self._query_rows(cache, ids32, add, K, ctx, append_at=pos, tail=None)
+        self._grown(cache, lengths, K)
+        return cache
+
+    def _replicate(self, cache, S):
+        """a cache of B*S scenes, scene b's S copies at b*S ... b*S+S-1, in buffers of its own"""
+        rep = cache.alias()
+        rep.kv = [kv.view(cache.B, -1).repeat_interleave(S, 0).view(-1, kv.shape[1]) for kv in cache.kv]
+        rep.B = cache.B * S
+        rep.lengths = None if cache.lengths is None else np.repeat(cache.lengths, S).astype(np.int32)
+        return rep
+
+    def rollout_from_context(self, cache, path_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 1, top_p: float = 1.0,
+                             seed: int = 0, return_logits: bool = False, fused_step: bool = True):
+        """A camera path whose frames agree with each other: ``path_cameras`` fp32 [B,T,7] in the context's (relative, normalised) frame.
+        For t = 0 ... T-1 view t is generated from the cache as it stands — the photographs AND the views 0 ... t-1 — and the generated
+        code map is appended with camera t: by definition the loop ``sample_from_context`` of 1 view (``view0 = t``), then
+        ``append_to_context``.  Codes are fed back on the device: no host synchronisation and no decode inside the loop.  -> dict of
+            codes           int64 [B,S,T,t,t]
+            token_log_prob  fp32  [B,S,T,t,t]  log p of each drawn code under the distribution it was drawn from (after the filters)
+            log_likelihood  fp32  [B,S,T]      its sum over a view's tokens, in token order
+            cache           the grown cache (T views longer; with S > 1 a replicated one of B*S scenes, ``cache`` itself untouched)
+        (``return_logits`` adds logits fp32 [B,S,T,t,t,n_embeddings]).  ``fused_step`` (default): one pass per step over 2 views per
+        scene — the append view of step t-1 and the MASK view of step t, ``ctx_len = (p, p+1)`` — with the last block's tail, ln_f and the
+        LM head on the MASK rows only, and a trailing append pass after step T-1; the MASK view's keys land in the cache's next free
+        view, beyond every length, where the next step's append view overwrites them.  ``fused_step=False``: the two passes of the
+        definition.  Both give the definition's bits where the dense layers take one kernel for both row counts.
+        ``top_k = 1`` (default) is the arg-max roll-out whatever the seed.  ``n_samples`` = S > 1: S independent trajectories per scene on
+        a cache replicated to B*S scenes (scene b's copies at b*S ... b*S+S-1); the noise of token l of step t of trajectory (b, s) is
+        keyed as ``sample_from_context`` keys scene b*S+s, view t, sample 0 — reproducible, and a prefix of a longer roll-out."""
+        path_cameras, L = self._check_growing(cache, path_cameras, 'rollout_from_context', 'path_cameras')
+        c, dev = self.config, self.device
+        d, nE, tshape = c.d_model, c.n_embeddings, cache.tshape
+        B, T, S = cache.B, path_cameras.shape[1], int(n_samples)
+        if not 1 <= S <= 65535 or S != n_samples:
+            raise ValueError(f'rollout_from_context: 1 <= n_samples <= 65535 expected, got {n_samples}')
+        if not (float(temperature) > 0 and math.isfinite(float(temperature))) or not float(top_p) > 0 or int(top_k) < 0:
+            raise ValueError(f'rollout_from_context: temperature > 0 (finite), top_p > 0 and top_k >= 0 expected, got {temperature}, {top_p}, {top_k}')
+        if T * L >= 1 << 32 or B * S >= 1 << 31:
+            raise ValueError(f'rollout_from_context: T * {L} < 2^32 and B * n_samples < 2^31 expected, got T = {T}, B = {B}, n_samples = {S}')
+        from .render import plan_rollout_lengths, plan_replication, rollout_row_ids
+        if S > 1:
+            cache = self._replicate(cache, S)
+            path_cameras = path_cameras[torch.from_numpy(plan_replication(B, S)).to(dev)]
+        Bs = B * S
+        M = Bs * L
+        lengths = cache.filled()
+        gen, pair = plan_rollout_lengths(lengths, T)                         # [T,Bs] and [T,Bs,2], host
+        codes, tlps, lls, lgs = [], [], [], []
+        if T:
+            self._reserve(cache, int(lengths.max()) + T)
+            gen_dev = torch.from_numpy(gen).to(dev)
+            pair_dev = torch.from_numpy(pair.reshape(T, Bs * 2)).to(dev)
+            pe = self._pose_embed(path_cameras)                              # [Bs,T,d]
+            row0 = torch.from_numpy(rollout_row_ids(Bs, 0, L)).to(dev)
+            mask_ids = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
+            prev = None
+            for t in range(T):
+                if t == 0 or not fused_step:
+                    if t:
+                        self._query_rows(cache, prev, pe[:, t - 1].contiguous(), 1, gen_dev[t - 1], append_at=gen_dev[t - 1], tail=None)
+                    hf = self._query_rows(cache, mask_ids, pe[:, t].contiguous(), 1, gen_dev[t])
+                else:
+                    ids = torch.stack([prev.view(Bs, L), mask_ids.view(Bs, L)], 1).reshape(2 * M)
+                    hf = self._query_rows(cache, ids, pe[:, t - 1:t + 1].reshape(Bs * 2, d), 2, pair_dev[t], append_at=gen_dev[t - 1], tail=1)
+                lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
+                self._lm(hf, M, lg)                                          # migt.py:417
+                st = ops.sample_rows(lg, M, nE, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, row_id=row0 + t * L, n_samples=1,
+                                     want=('idx', 'logp'))
+                lls.append(ops.sample_views(st['logp'], Bs, L, 1).view(Bs))  # one fp32 chain per view, in token order
+                prev = st['idx'].view(M).to(torch.int32)
+                codes.append(st['idx'].view(Bs, L)); tlps.append(st['logp'].view(Bs, L))
+                if return_logits:
+                    lgs.append(lg.view(Bs, L, nE))
+            self._query_rows(cache, prev, pe[:, T - 1].contiguous(), 1, gen_dev[T - 1], append_at=gen_dev[T - 1], tail=None)
+            self._grown(cache, lengths, T)
+        stack = lambda xs, dt, *tail: (torch.stack(xs, 1) if xs else torch.empty((Bs, 0, *tail), dtype=dt, device=dev))
+        res = dict(codes=stack(codes, torch.int64, L).view(B, S, T, *tshape), token_log_prob=stack(tlps, torch.float32, L).view(B, S, T, *tshape),
+                   log_likelihood=stack(lls, torch.float32).view(B, S, T), cache=cache)
+        if return_logits:
+            res['logits'] = stack(lgs, torch.float32, L, nE).view(B, S, T, *tshape, nE)
+        return res
 
     def generate_and_localize(self, codes, cameras, codes_only: bool = False):
         """The evaluator's two transformer passes (evaluate_transformer.py:119-123 and :134-136) as ONE pass.

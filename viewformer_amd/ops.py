@@ -624,6 +624,24 @@ def attn_prefix(q, k, v, kp, vp, out, B, H, C, N, L, ldq, ldk, ldv, ldkp, ldvp, 
     return out
 
 
+def kv_append(qkv, cache, B, K, L, d, ld_src, ld_dst, cache_stride, capacity, pos):
+    """Append the keys and values of K new views per scene to a context cache with room (csrc/kv_append.hip): ``qkv`` = the new views'
+    fused c_attn output, rows [B*K*L] of leading dimension ``ld_src``, thirds (V, Q, K); the V and K thirds of new view j of scene b go
+    to the cache's view ``pos[b] + j`` (``cache``: ``capacity`` views of L rows per scene, leading dimension ``ld_dst``, scenes
+    ``cache_stride`` elements apart), bit for bit, bf16 or fp32 (one dtype for both tensors).  ``pos``: int32 device tensor [B], each
+    scene's own length.  One launch; nothing else of ``cache`` changes."""
+    if qkv.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'kv_append: bf16 or fp32 tensors expected, got {qkv.dtype}')
+    _chk(cache, qkv.dtype, 'cache')
+    _chk(qkv, qkv.dtype, 'qkv')
+    _chk(pos, torch.int32, 'pos')
+    if pos.numel() != B or not pos.is_contiguous():
+        raise ValueError(f'kv_append: pos int32 [B = {B}] contiguous expected, got {tuple(pos.shape)}')
+    check(_lib.load().vf_kv_append(_p(qkv), _p(cache), qkv.element_size(), B, K, L, d, ld_src, ld_dst, cache_stride, capacity, _p(pos),
+                                   _stream()), 'vf_kv_append')
+    return cache
+
+
 def attn_spatial_supported(HW, C):
     return (HW, C) in ((256, 256), (64, 512), (64, 256))
 

@@ -13,6 +13,8 @@ and values are computed once (``MIGT.prefill_context``) and each query is a sing
     est = r.localize(images=photos_u8)                       # est['generated_cameras'] fp32 [B,N,7], the caller's world frame
     fit = r.score(candidate_cameras, images=photo_u8)        # fit['log_likelihood'] fp32 [B,N]: how well the photo fits each camera
     alt = r.sample(query_cameras, n_samples=8, top_p=0.9)    # alt['generated_images'] uint8 [B,N,8,H,W,3]: draws, with their log-likelihood
+    r.append(images=new_frames_u8, cameras=new_cams)         # new photographs: the context grows by K views, no earlier view is run again
+    fly = r.rollout(path_cameras)                            # fly['generated_images'] uint8 [B,T,H,W,3]: frame t sees the photos AND frames 0..t-1
 
 Contract: ``render(q)['generated_images'][b, n]`` is what ``generate_batch_predictions`` generates for the scene (context views of b...,
 any frame) with cameras (context cameras of b..., q[b, n]); ``localize(photos)['generated_cameras'][b, n]`` is what it returns as
@@ -28,7 +30,18 @@ view 0 camera by camera, so the first c views of a C-view cache ARE the cache of
 tiles (``ops.attn_prefix(ctx_len=...)``): ``sweep`` answers "how good is the view from 0, 1, ..., C photos" from one prefill, and
 ``evaluate_context_sizes`` is the cached drop-in for ``evaluate_multictx.generate_batch_predictions``.
 
-Not covered here: contexts that change per query (the 7-Scenes pose-refinement loop); it keeps its evaluator.
+A context that grows: for the same three reasons a view added BEHIND the cached ones changes none of them.  A cache
+with room (``set_context(capacity=...)``; otherwise it is reallocated, doubling) takes the keys and values of new views in every layer
+(``ops.kv_append``), and a new view attends to the cache, the new views before it and itself through the same prefix attention:
+``append`` costs the K new views and nothing else, and ``rollout`` generates a camera path autoregressively — frame t from the photographs
+and the frames 0 ... t-1 — in one two-view pass per step, codes fed back on the device.  Contract: ``append(x, cams)`` after
+``set_context(ctx, ctx_cams)`` answers every later call as ``set_context(cat(ctx, x), cat(ctx_cams, cams))`` would, within the arm's own
+error (the same launches per row, except that a prefilled view's attention is the block-causal kernel and an appended view's the prefix
+kernel); ``rollout(path)`` is the loop
+"``sample`` one view at path[t] (``top_k = 1``: ``render``), ``append`` it with path[t]".
+
+Not covered here: contexts that change per query other than by growing at the end (the 7-Scenes pose-refinement loop; sliding windows or
+eviction, which would change what the later views' keys are); they keep their evaluator.
 """
 import numpy as np
 import torch
@@ -111,6 +124,43 @@ def sweep_layout(N: int, K: int):
     return (j % N if N else j), (j // N if N else j), inverse
 
 
+def plan_capacity(capacity: int, needed: int) -> int:
+    """The capacity (views per scene) of a cache that must hold ``needed`` views: ``capacity`` while it suffices, else
+    max(2 capacity, needed) — doubling, so that T appends of one view reallocate O(log T) times.  Pure."""
+    capacity, needed = int(capacity), int(needed)
+    if capacity < 0 or needed < 0:
+        raise ValueError(f'plan_capacity: capacity >= 0 and needed >= 0 expected, got {capacity} and {needed}')
+    return capacity if needed <= capacity else max(2 * capacity, needed)
+
+
+def plan_rollout_lengths(lengths, T: int):
+    """Context lengths of a T-step roll-out from scenes of ``lengths`` [B] filled views: (gen int32 [T,B], pair int32 [T,B,2]).
+    ``gen[t, b] = lengths[b] + t``: what the MASK view of step t sees (the context and the generated views 0 ... t-1), and also the
+    cache view that the generated view t is appended at, seeing as many.  ``pair[t, b]`` = (gen[t-1, b], gen[t, b]): the fused step's
+    two views per scene, the append view of step t-1 and the MASK view of step t (row 0, which has no append view, is not used).  Pure."""
+    a = np.asarray(lengths)
+    if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or T < 0 or (a.size and a.min() < 0):
+        raise ValueError(f'plan_rollout_lengths: lengths, [B] integers >= 0, and T >= 0 expected, got {lengths} and {T}')
+    gen = (a.astype(np.int64).reshape(1, -1) + np.arange(T, dtype=np.int64).reshape(T, 1)).astype(np.int32)
+    pair = np.stack([gen - 1, gen], -1)
+    return np.ascontiguousarray(gen), np.ascontiguousarray(pair)
+
+
+def plan_replication(B: int, S: int):
+    """Scene of the original batch behind each scene of a batch replicated S times: int64 [B*S], scene b's copies at b*S ... b*S+S-1.  Pure."""
+    if B < 0 or S < 1:
+        raise ValueError(f'plan_replication: B >= 0 and S >= 1 expected, got {B} and {S}')
+    return np.repeat(np.arange(B, dtype=np.int64), S)
+
+
+def rollout_row_ids(n_scenes: int, t: int, L: int):
+    """Noise keys of step t of a roll-out over ``n_scenes`` (= B*S) scenes: int64 [n_scenes*L], (scene << 32) | (t L + l) — what
+    ``MIGT.sample_from_context`` gives view ``t`` of that scene (``view0 = t``), so a trajectory's draws do not depend on T.  Pure."""
+    if n_scenes < 0 or t < 0 or L < 1 or (t + 1) * L > 1 << 32:
+        raise ValueError(f'rollout_row_ids: n_scenes >= 0, t >= 0, L >= 1 and (t + 1) L <= 2^32 expected, got {n_scenes}, {t}, {L}')
+    return ((np.arange(n_scenes, dtype=np.int64) << 32).reshape(-1, 1) + (np.arange(L, dtype=np.int64) + t * L).reshape(1, L)).reshape(-1)
+
+
 class ViewRenderer:
     def __init__(self, transformer_model, codebook_model):
         self.transformer = transformer_model
@@ -122,13 +172,15 @@ class ViewRenderer:
         self.fused_score = None            # score: None = MIGT.score_from_context's default route, True / False = the fused LM head / through the logits
         self.fused_tail = None             # localize: None = MIGT.localize_from_context's default tail, True / False = the fused / unfused one
 
-    def set_context(self, images=None, cameras=None, codes=None, n_context=None):
+    def set_context(self, images=None, cameras=None, codes=None, n_context=None, capacity=None):
         """``images`` uint8 [B,C,H,W,3] (host or device; resized for the encoder as the evaluators do) or ``codes`` int [B,C,t,t]
         (already encoded, e.g. ``SceneBank.gather``), and ``cameras`` [B,C,7] in the caller's world frame.  Encodes once, prefills the
         transformer's key / value cache once.  ``n_context``: [B] (or an int), the number of valid context views per scene in [1, C],
         for a ragged batch padded to C: scene b's queries see its first ``n_context[b]`` views only (the default of ``render``,
         ``sample``, ``score``, ``localize`` and ``sweep``).  Padding views must hold valid code ids (or images) and finite cameras; they
-        are computed by the prefill and never read by a query.  View 0 is valid in every scene, so the poses' frame is each scene's own."""
+        are computed by the prefill and never read by a query.  View 0 is valid in every scene, so the poses' frame is each scene's own.
+        ``capacity`` >= C: room for that many views per scene (``MIGT.prefill_context``), so that ``append`` and ``rollout`` need not
+        reallocate; None: the tight cache, which grows at the first of them."""
         tm, cm = self.transformer, self.codebook
         dev = cm.device
         if cameras is None or (images is None) == (codes is None):
@@ -156,9 +208,106 @@ class ViewRenderer:
             if codes.numel() != B * C * t * t:
                 raise ValueError(f'set_context: codes {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
         codes = codes.to(torch.int32).view(B, C, t, t)
-        self.cache = tm.prefill_context(codes, poses)
+        self.cache = tm.prefill_context(codes, poses) if capacity is None else tm.prefill_context(codes, poses, capacity=capacity)
         self.transform, self.context_codes, self.n_context = transform, codes, n_context
         return self
+
+    def _own_lengths(self, cache):
+        """before the context grows: a ragged batch's valid views (``set_context(n_context=...)``) become the cache's own lengths, so
+        that new views go behind each scene's valid views (over its padding)"""
+        if self.n_context is not None and cache.lengths is None:
+            cache.lengths = np.array(self.n_context, dtype=np.int32)
+            cache.C = int(cache.lengths.max())
+        return cache
+
+    def _add_codes(self, before, codes):
+        """context_codes [B,C,t,t] with ``codes`` [B,K,t,t] behind each scene's ``before[b]`` valid maps (padded to the longest scene)"""
+        B, K = codes.shape[:2]
+        old = self.context_codes
+        C = int(before.max()) + K
+        out = torch.zeros((B, max(C, old.shape[1]), *old.shape[2:]), dtype=old.dtype, device=old.device)
+        out[:, :old.shape[1]] = old
+        at = torch.from_numpy(before.astype(np.int64).reshape(B, 1) + np.arange(K, dtype=np.int64).reshape(1, K)).to(old.device)
+        out[torch.arange(B, device=old.device).view(B, 1), at] = codes.to(old.dtype)
+        self.context_codes = out[:, :C]
+        if self.n_context is not None:
+            self.n_context = (before + K).astype(np.int32)
+
+    def append(self, images=None, codes=None, cameras=None):
+        """New photographs arrive: ``images`` uint8 [B,K,H,W,3] (encoded once, as ``set_context`` encodes) or ``codes`` int [B,K,t,t], and
+        ``cameras`` [B,K,7] in the caller's world frame (the context's: view 0 stays the frame).  The context grows in place by K views
+        per scene in one pass over the new views (``MIGT.append_to_context``): no earlier view is run again.  Every later ``render``,
+        ``sample``, ``score``, ``localize`` and ``sweep`` sees the grown context; ``n_context`` and ``context_codes`` follow."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.append: set_context() first')
+        if cameras is None or (images is None) == (codes is None):
+            raise ValueError('append: cameras and exactly one of images / codes expected')
+        tm, cm = self.transformer, self.codebook
+        dev = cm.device
+        B = self.cache.B
+        t = tm.config.token_image_size
+        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(dev)
+        if cameras.dim() != 3 or cameras.shape[0] != B or cameras.shape[-1] != 7:
+            raise ValueError(f'append: cameras [B={B},K,7] expected, got {tuple(cameras.shape)}')
+        K = cameras.shape[1]
+        if codes is None:
+            images = torch.as_tensor(images).to(dev)
+            if images.dim() != 5 or tuple(images.shape[:2]) != (B, K):
+                raise ValueError(f'append: images [B,K,H,W,3] with one frame per camera of {tuple(cameras.shape)} expected, got {tuple(images.shape)}')
+            codes = (cm.encode(_frames_for_encode(images, cm.config.image_size))[-1] if K
+                     else torch.empty((B, 0, t, t), dtype=torch.int32, device=dev))
+        else:
+            codes = torch.as_tensor(codes).to(dev)
+            if codes.numel() != B * K * t * t or codes.dtype.is_floating_point:
+                raise ValueError(f'append: codes int {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
+        codes = codes.to(torch.int32).view(B, K, t, t)
+        self._own_lengths(self.cache)
+        before = self.cache.filled()
+        tm.append_to_context(self.cache, codes, query_poses(cameras, self.transform))
+        self._add_codes(before, codes)
+        return self
+
+    def rollout(self, path_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 1, top_p: float = 1.0, seed: int = 0,
+                return_codes: bool = False, keep: bool = True, fused_step: bool = None):
+        """A fly-through whose frames agree with each other: ``path_cameras`` [B,T,7] in the caller's world frame.  Frame t is generated
+        from the photographs AND the frames 0 ... t-1 (``MIGT.rollout_from_context``: the model's autoregressive answer), where
+        ``render(path)`` draws every frame from the photographs alone -> dict(generated_images uint8 [B,T,H,W,3], log_likelihood fp32
+        [B,T]) — [B,S,T,...] for ``n_samples`` = S > 1, S independent trajectories; with ``return_codes`` also generated_codes int64,
+        token_log_prob fp32 [B,(S,)T,t,t] and logits fp32 [B,(S,)T,t,t,n_embeddings].  ``top_k = 1`` (default) is the arg-max roll-out;
+        ``temperature``, ``top_k``, ``top_p`` and ``seed`` as ``sample``.  Nothing is decoded inside the loop: the T maps are decoded
+        afterwards in chunks of MAX_SCENES_PER_CALL.  ``keep`` (default, S = 1): the generated frames stay in the context, as ``append``
+        would leave them; ``keep=False`` rolls out on a copy of the lengths and leaves the renderer's context as it was (the appended
+        rows are beyond its lengths again).  With S > 1 the roll-out runs on a replicated cache and the renderer's own is never
+        replaced.  ``fused_step``: None = the model's default step, True / False = the one-pass / two-pass step, for A/B runs."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.rollout: set_context() first')
+        tm, cm = self.transformer, self.codebook
+        dev = cm.device
+        B = self.cache.B
+        path_cameras = torch.as_tensor(path_cameras, dtype=torch.float32).to(dev)
+        if path_cameras.dim() != 3 or path_cameras.shape[0] != B or path_cameras.shape[-1] != 7:
+            raise ValueError(f'rollout: path_cameras [B={B},T,7] expected, got {tuple(path_cameras.shape)}')
+        S = int(n_samples)
+        if S < 1 or S != n_samples:
+            raise ValueError(f'rollout: n_samples >= 1 expected, got {n_samples}')
+        T = path_cameras.shape[1]
+        t = tm.config.token_image_size
+        grow = keep and S == 1
+        work = self._own_lengths(self.cache if grow else self.cache.alias())
+        before = work.filled()
+        kw = {} if fused_step is None else dict(fused_step=bool(fused_step))
+        out = tm.rollout_from_context(work, query_poses(path_cameras, self.transform), n_samples=S,
+                                      temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, return_logits=return_codes, **kw)
+        codes = out['codes']                                             # [B,S,T,t,t]
+        if grow and T:
+            self._add_codes(before, codes[:, 0].to(torch.int32))
+        img, _ = self._decode(codes.reshape(B * S * T, t, t))
+        lead = (B, T) if S == 1 else (B, S, T)
+        res = dict(generated_images=img.view(*lead, *img.shape[1:]), log_likelihood=out['log_likelihood'].view(*lead))
+        if return_codes:
+            res.update(generated_codes=codes.view(*lead, t, t), token_log_prob=out['token_log_prob'].view(*lead, t, t),
+                       logits=out['logits'].view(*lead, t, t, out['logits'].shape[-1]))
+        return res
 
     def _decode(self, flat, keep_decoded: bool = False):
         """code maps int [n,t,t] -> (images uint8 [n,H,W,3], the decoder's fp32 output [n,H,W,3] or None), decoded in chunks of
@@ -447,6 +596,18 @@ def sample_views(transformer_model, codebook_model, images, cameras, query_camer
     ``seed``, ``max_views_per_call``, ``return_codes``."""
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
     return r.sample(query_cameras, **kw)
+
+
+def rollout_views(transformer_model, codebook_model, images, cameras, path_cameras, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``path_cameras`` [B,T,7] -> ``ViewRenderer.rollout``'s
+    dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``n_context`` (valid context views per scene),
+    ``n_samples``, ``temperature``, ``top_k``, ``top_p``, ``seed``, ``return_codes``, ``fused_step``.  The cache is allocated with room
+    for the whole path."""
+    T = int(torch.as_tensor(path_cameras).shape[1])
+    C = int(torch.as_tensor(cameras).shape[1])
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None),
+                                                                    n_context=kw.pop('n_context', None), capacity=C + T)
+    return r.rollout(path_cameras, **kw)
 
 
 def score_views(transformer_model, codebook_model, images, cameras, query_cameras, photos=None, **kw):
