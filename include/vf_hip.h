@@ -307,6 +307,25 @@ int vf_attn_prefix_var_bf16(const void* q, const void* k, const void* v, const v
 int vf_attn_prefix_var_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
                              int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                              int ldo, const int32_t* ctx_len, void* stream);
+/* Backward of the prefix-cache attention over the QUERY views (csrc/attention_prefix_bwd.hip; MIGT.score_grad_from_context): the inputs of
+ * vf_attn_prefix_var_* — q / k / v, the query views' thirds of the fused c_attn output, rows [B*N*L]; kp / vp, the cache with ld*,
+ * prefix_stride and capacity C; ctx_len, a device pointer to [B*N] int32 (clamped to [0, C] on read) or NULL for "all C views" — plus
+ * dout, fp32 [B*N*L][lddo], the gradient of the attention output.  in_bf16: q / k / v / kp / vp are bf16 storage (ld*, prefix_stride % 8)
+ * or fp32 (% 4); either way operands are widened to fp32 on load and every product runs on the fp32-input MFMA: one kernel for both arms.
+ * Output dqkv, fp32 [B*N*L][lddqkv], in the c_attn column order (V, Q, K): dV of the view's own keys in columns [0, d), dQ in [d, 2d), dK of
+ * its own keys in [2d, 3d), d = 64 H.  The cache is a constant of the query (nothing flows into it).  O, lse and D = rowsum(dO * O) are
+ * recomputed in fp32 from the operands as stored; scores are un-scaled, as in the forward.  One workgroup per (scene, view, head), tiles in
+ * a fixed order (prefix ascending, own tile last), no atomics.  Contract:
+ *   - a view's result is bit-identical whatever N, its position and the other views' lengths, and equals the result with C = ctx_len on the
+ *     same buffers and prefix_stride;
+ *   - it does not depend on cache rows at or beyond the view's length (they are not read);
+ *   - the 3 d logical columns of every row of dqkv are written, each once, and nothing else: no zero-fill is required of the caller.
+ * L = 64, dh = 64, C >= 1: anything else VF_ERR_UNSUPPORTED before any launch (as B, N or H above 65535); NULL q / k / v / kp / vp / dout /
+ * dqkv, ld* < H * 64, lddqkv < 3 * H * 64 or misaligned (lddo, lddqkv % 4; q / k / v / kp / vp not 8-byte (bf16) or 16-byte (fp32) aligned,
+ * dout / dqkv not 16-byte aligned): VF_ERR_BAD_ARG; B = 0 or N = 0: no-op, VF_OK. */
+int vf_attn_prefix_bwd_f32(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, const float* dout,
+                           float* dqkv, int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp,
+                           int64_t prefix_stride, int lddo, int lddqkv, const int32_t* ctx_len, void* stream);
 /* Append the keys and values of K new views per scene to a context cache with room (csrc/kv_append.hip): qkv = the fused c_attn output of
  * the new views, rows [B*K*L][ld_src], thirds (V, Q, K); for scene b and new view j the V third (columns [0, d)) and the K third (columns
  * [2d, 3d)) of the view's L rows are copied to rows (pos[b] + j) L ... of scene b of `cache` (leading dimension ld_dst, scenes cache_stride

@@ -103,6 +103,7 @@ EXPORTS = {
     'vf_attn_prefix_f32eq': (c_int, [P, P, P, P, P, P] + [c_int] * 11 + [c_int64, c_int, P]),
     'vf_attn_prefix_var_bf16': (c_int, [P, P, P, P, P, c_int, P, c_int] + [c_int] * 11 + [c_int64, c_int, P, P]),
     'vf_attn_prefix_var_f32eq': (c_int, [P, P, P, P, P, P] + [c_int] * 11 + [c_int64, c_int, P, P]),
+    'vf_attn_prefix_bwd_f32': (c_int, [P, P, P, P, P, c_int, P, P] + [c_int] * 11 + [c_int64, c_int, c_int, P, P]),
     'vf_kv_append': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, P, P]),
     'vf_attn_blockcausal_lse_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                             c_float, c_int, c_int, c_float, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]),

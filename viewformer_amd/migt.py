@@ -107,6 +107,7 @@ class MIGT:
         self.skip_masked = skip_masked
         self._sd_host = None
         self._dense = {}
+        self._dense_t = {}
         self._ln = {}
         self._weights_version = 0                             # counts uploads: a ContextCache is tied to the weights that filled it
 
@@ -210,6 +211,7 @@ class MIGT:
             for p in ('attn.c_attn', 'attn.c_proj', 'mlp.c_fc', 'mlp.c_proj'):
                 dense(f'h.{i}.{p}')
         ln('ln_f')
+        self._dense_t = {}                                                   # transposed packs (_dense_T) belong to the weights they were made from
         self._weights_version += 1
         torch.cuda.synchronize(dev)
 
@@ -406,7 +408,7 @@ class MIGT:
                 raise ValueError(f'n_context: at most the filled views of each scene ({cache.lengths.tolist()}) expected, got {plan.max(1).tolist()}')
         return torch.from_numpy(plan.reshape(-1)).to(self.device)
 
-    def _query_rows(self, cache, ids32, add, N, n_context=None, append_at=None, tail='all'):
+    def _query_rows(self, cache, ids32, add, N, n_context=None, append_at=None, tail='all', save=None):
         """The per-layer loop over the rows of N query views per scene of ``cache``: ``ids32`` int32 [B*N*L] token ids, ``add`` fp32
         [B*N, d] (a pose embedding or the LOC row per view) -> ln_f hidden states [B*N*L, d].  Each view attends to the cached context
         and to itself (ops.attn_prefix); its rows go through the LayerNorm / dense launches of the full pass.  ``n_context``: None, or an
@@ -419,9 +421,15 @@ class MIGT:
         view n attends to the old context, to the views 0 ... n-1 of this pass and to itself: block-causal attention, same kernel.
         ``tail``: 'all' (the hidden states of every row), a view number n (the last block's projection, MLP and ln_f on that view's
         rows only -> [B*L, d]; the rows that are returned keep their bits) or None (nothing is returned: the last block ends once its
-        keys and values are in the cache)."""
+        keys and values are in the cache).
+        ``save``: None (the path and the launches without the keyword), or a list that receives what a backward pass over these rows
+        needs (``score_grad_from_context``): per layer the tuple (the block's input h, the residual stream after the attention, the
+        layer's fused c_attn output in a buffer of its own, the LayerNorm-2 output), then the final h that ``ln_f`` reads.  Same launches
+        on the same values: the hidden states keep their bits.  With ``tail='all'`` only."""
         c, dev = self.config, self.device
         B, C = cache.B, cache.capacity                                       # the attention's C is the room: lengths say what is filled
+        if save is not None and tail != 'all':
+            raise ValueError('_query_rows: save goes with tail="all" (a backward pass needs every row)')
         L = int(np.prod(cache.tshape))
         d, H, nE = c.d_model, c.n_head, c.n_embeddings
         M = B * N * L
@@ -435,6 +443,9 @@ class MIGT:
             p = f'h.{i}'
             last = i == c.n_layer - 1
             a = ops.layernorm(h, *self._ln[p + '.ln_1'], M, d, out_bf16=act16)
+            if save is not None and i:
+                qkv = torch.empty_like(qkv)                                  # the backward reads every layer's q / k / v again
+            h_in = h
             self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
             ckv = cache.kv[i]                                                # [B*capacity*L, 3d], thirds (V, Q, K)
             if append_at is not None:
@@ -451,8 +462,12 @@ class MIGT:
                 h = h.view(B, N, L, d)[:, tail].reshape(M, d)
             h = self._gemm(att_i, p + '.attn.c_proj', M, res=h)
             m = ops.layernorm(h, *self._ln[p + '.ln_2'], M, d, out_bf16=act16)
+            if save is not None:
+                save.append((h_in, h, qkv, m))
             f = self._gemm(m, p + '.mlp.c_fc', M, epilogue=ops.EPI_GELU, out_bf16=act16)
             h = self._gemm(f, p + '.mlp.c_proj', M, res=h)
+        if save is not None:
+            save.append(h)
         return ops.layernorm(h, *self._ln['ln_f'], M, d)                     # migt.py:408
 
     def generate_from_context(self, cache, query_cameras, codes_only: bool = True, return_confidence: bool = False, n_context=None):
@@ -547,6 +562,195 @@ class MIGT:
         tlp, conf, ll, acc = ops.score_views(st, target, B * N, L)           # log-likelihood: one fp32 chain per view, in token order
         return dict(token_log_prob=tlp.view(B, N, *tshape), log_likelihood=ll.view(B, N), predicted_codes=st['idx'].view(B, N, *tshape),
                     confidence=conf.view(B, N, *tshape), entropy=st['entropy'].view(B, N, *tshape), accuracy=acc.view(B, N))
+
+    # ------------------------------------------------------------------ gradient of the score with respect to the query cameras
+    def _dense_T(self, name):
+        """the native-fp32 TRANSPOSED pack of a dense layer, for dx = dy @ W^T on ``ops.igemm`` (MIGTTrainer._linear_dx's last branch), made
+        on first use and kept until the weights are replaced; ``'wte'``: ``wte[:n_embeddings]`` as an [n_embeddings -> d] layer, the
+        transpose of the tied LM head"""
+        t = self._dense_t.get(name)
+        if t is None:
+            if name == 'wte':
+                c = self.config
+                t = ops.pack(self._wte, c.n_embeddings, c.d_model, 1, sk=c.d_model, sn=1, st=0)
+            else:
+                dn = self._dense[name]
+                t = ops.pack(dn.w_raw, dn.n, dn.k, 1, sk=1, sn=dn.n, st=0)
+            self._dense_t[name] = t
+        return t
+
+    def _linear_dx(self, name, dy, M, res=None):
+        """dx [M, k] = dy [M, n] @ W^T (+ res) in native fp32, whatever the arm of the forward"""
+        if name == 'wte':
+            k, n = self.config.d_model, self.config.n_embeddings
+        else:
+            k, n = self._dense[name].k, self._dense[name].n
+        dx = torch.empty((M, k), dtype=torch.float32, device=dy.device)
+        ops.igemm(dy, self._dense_T(name), M, n, k, dx, res=res)
+        return dx
+
+    def _pose_embed_bwd(self, poses, dadd):
+        """backward of ``_pose_embed``: ``dadd`` fp32 [B*N, d], the gradient of the pose embedding -> the gradient of ``poses`` [B,N,7]
+        (the 7 numbers free).  c_proj^T, the exact-erf GELU's derivative at the recomputed pre-activation, c_fc^T (a layer with 7
+        outputs: ``dense_small_n`` where its shape rule admits, else the native GEMM), then the pose multiplier on the position columns."""
+        from . import train_ops as T
+        B, Sp, _ = poses.shape
+        c = self.config
+        R = B * Sp
+        fc = self._dense['pose_embedding.c_fc']
+        pin = geometry.pose_model_input(poses, c.pose_multiplier).reshape(R, 7).contiguous()
+        u = ops.dense_small_k(pin, fc.w_raw, fc.bias, R, 7, fc.n, gelu=False)
+        du = T.gelu_bwd(u, self._linear_dx('pose_embedding.c_proj', dadd, R))
+        if T.dense_small_n_supported(fc.n, fc.k):
+            wt = self._dense_t.get('pose_embedding.c_fc.T')
+            if wt is None:
+                wt = self._dense_t['pose_embedding.c_fc.T'] = T.transpose(fc.w_raw, fc.k, fc.n).view(fc.n, fc.k)
+            dpin = T.dense_small_n(du, wt, None, R, fc.n, fc.k)
+        else:
+            dpin = self._linear_dx('pose_embedding.c_fc', du, R)
+        # (a Python scalar: a constant built on the host would be a blocking copy, and a synchronise, in every pass)
+        return torch.cat([dpin[:, :3] * c.pose_multiplier, dpin[:, 3:]], -1).view(B, Sp, 7)
+
+    def _score_backward(self, cache, poses, ids32, lg, target, saved, N, ctx):
+        """d sum_tokens log p(code) / d poses [B,N,7] from what ``_query_rows(save=...)`` kept: every step a HIP launch of the training
+        step's kernels in fp32 (train_ops.py), the attention's by ``ops.attn_prefix_bwd``.  The cache is a constant of the query camera
+        (DESIGN.md §6.16), so the gradient stops there; weight gradients go to scratch and are dropped."""
+        from . import train_ops as T
+        c, dev = self.config, self.device
+        B, C = cache.B, cache.capacity
+        L = int(np.prod(cache.tshape))
+        d, H, nE = c.d_model, c.n_head, c.n_embeddings
+        M = B * N * L
+        dgam, dbet = torch.empty(d, dtype=torch.float32, device=dev), torch.empty(d, dtype=torch.float32, device=dev)
+        # + log-likelihood: dlogits = onehot - softmax = (softmax - onehot) * (-1).  A code outside [0, n_embeddings) has log-probability
+        # -inf and no gradient: its row gets weight 0 (and a target inside the row, which the kernel reads)
+        valid = (target >= 0) & (target < nE)
+        w = torch.where(valid, -1.0, 0.0).to(torch.float32)
+        _, dlg = T.softmax_ce(lg, target.clamp(0, nE - 1), w, M, nE)
+        dh = self._linear_dx('wte', dlg, M)
+        dh = T.layernorm_bwd(dh, saved[-1], self._ln['ln_f'][0], dgam, dbet, M, d, accumulate=False)
+        for i in reversed(range(c.n_layer)):
+            p = f'h.{i}'
+            h_in, h_mid, qkv, m = saved[i]
+            df = self._linear_dx(p + '.mlp.c_proj', dh, M)
+            u = self._gemm(m, p + '.mlp.c_fc', M)                            # the pre-activation again, without the GELU epilogue
+            dm = self._linear_dx(p + '.mlp.c_fc', T.gelu_bwd(u, df), M)
+            dh = T.layernorm_bwd(dm, h_mid, self._ln[p + '.ln_2'][0], dgam, dbet, M, d, accumulate=False, res=dh)
+            datt = self._linear_dx(p + '.attn.c_proj', dh, M)
+            ckv = cache.kv[i]
+            dqkv = torch.empty((M, 3 * d), dtype=torch.float32, device=dev)
+            ops.attn_prefix_bwd(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], datt, dqkv, B, H, C, N, L,
+                                3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, 3 * d, ctx_len=ctx)
+            da = self._linear_dx(p + '.attn.c_attn', dqkv, M)
+            dh = T.layernorm_bwd(da, h_in, self._ln[p + '.ln_1'][0], dgam, dbet, M, d, accumulate=False, res=dh)
+        dwte = torch.empty((nE + 2, d), dtype=torch.float32, device=dev)
+        dwpe = torch.empty_like(self._wpe)
+        dadd = T.embed_bwd(dh, ids32, dwte, dwpe, B * N, L, d, nE + 2)
+        return self._pose_embed_bwd(poses, dadd)
+
+    def score_grad_from_context(self, cache, query_cameras, codes, n_context=None):
+        """``score_from_context`` (through the logits: its ``fused=False`` route, the same launches, every key with the same bits) plus
+            grad_cameras  fp32 [B,N,7]   d log_likelihood[b,n] / d query_cameras[b,n], the 7 numbers treated as free
+        — which way each camera should move so that its photo fits better.  One backward pass over the query rows in fp32 on both
+        arms (``_score_backward``); the cached context is a constant of the query camera, so nothing flows into the cache.  The
+        gradient of a view depends on that view alone.  A code outside [0, n_embeddings) (log-probability -inf) contributes no
+        gradient.  ``n_context``: as ``score_from_context``'s."""
+        query_cameras, codes, N, ctx = self._score_grad_args('score_grad_from_context', cache, query_cameras, codes, n_context)
+        return self._score_grad(cache, query_cameras, codes, N, ctx)
+
+    def _score_grad_args(self, what, cache, query_cameras, codes, n_context):
+        """``score_from_context``'s validation, in its order -> (cameras and codes on the device, N, the context lengths as
+        ``_context_lengths`` makes them: None or an int32 device tensor [B*N], planned on the host and copied once)"""
+        if not isinstance(cache, ContextCache):
+            raise TypeError(f'{what}: a ContextCache from prefill_context expected')
+        B, tshape = cache.B, cache.tshape
+        L = int(np.prod(tshape))
+        self._check_render_shapes(L)
+        cache.check(self)
+        c, dev = self.config, self.device
+        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
+        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
+            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
+        N = query_cameras.shape[1]
+        codes = torch.as_tensor(codes).to(dev)
+        if (codes.dim() != 2 + len(tshape) or codes.shape[0] != B or codes.shape[1] not in (1, N) or tuple(codes.shape[2:]) != tshape
+                or codes.dtype.is_floating_point or codes.dtype == torch.bool):
+            raise ValueError(f'codes int [B={B},N={N} or 1,{",".join(map(str, tshape))}] expected, got {codes.dtype} {tuple(codes.shape)}')
+        return query_cameras, codes, N, self._context_lengths(cache, n_context, N)      # validated on the host before any launch
+
+    def _score_grad(self, cache, query_cameras, codes, N, ctx):
+        """``score_grad_from_context`` on validated device tensors and prepared context lengths: launches only, nothing here waits for
+        the device or copies from the host (tests/test_hip_score_grad.py runs it under torch's synchronisation check)"""
+        c, dev = self.config, self.device
+        B, tshape = cache.B, cache.tshape
+        L = int(np.prod(tshape))
+        d, nE = c.d_model, c.n_embeddings
+        M = B * N * L
+        if N == 0:
+            res = self.score_from_context(cache, query_cameras, codes)
+            res['grad_cameras'] = torch.empty((B, 0, 7), dtype=torch.float32, device=dev)
+            return res
+        target = codes.to(torch.int32).expand(B, N, *tshape).reshape(M).contiguous()
+        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
+        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
+        saved = []
+        hf = self._query_rows(cache, ids32, add, N, ctx, save=saved)
+        lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
+        self._lm(hf, M, lg)                                                  # migt.py:417
+        st = ops.logits_score(lg, M, nE, target=target)
+        tlp, conf, ll, acc = ops.score_views(st, target, B * N, L)
+        grad = self._score_backward(cache, query_cameras, ids32, lg, target, saved, N, ctx)
+        return dict(token_log_prob=tlp.view(B, N, *tshape), log_likelihood=ll.view(B, N), predicted_codes=st['idx'].view(B, N, *tshape),
+                    confidence=conf.view(B, N, *tshape), entropy=st['entropy'].view(B, N, *tshape), accuracy=acc.view(B, N),
+                    grad_cameras=grad)
+
+    def refine_from_context(self, cache, cameras0, codes, steps: int = 16, step_xyz: float = 0.05, step_rot: float = 0.05, n_context=None,
+                            return_trace: bool = False):
+        """Move cameras so that their photos fit better: a monotone gradient ascent on ``log_likelihood`` per view, from ``cameras0``
+        fp32 [B,N,7] (the cache's frame, scored as they are given) with ``codes`` as ``score_from_context`` takes them.
+        Every step proposes ``render.ascend_poses(p, g, s_xyz, s_rot)`` for all views — a step of length s_xyz along the position
+        gradient and of s_rot along the tangent part of the quaternion gradient — and scores the candidates in ONE
+        ``score_grad_from_context`` pass; a view whose log-likelihood rose takes its candidate and the gradient there, every other view
+        keeps its camera and gradient and halves both of its steps.  Arguments are validated, brought to the device and (``n_context``, or a
+        cache with slack or lengths of its own) turned into a device tensor of context lengths ONCE, before the first pass; after that
+        nothing synchronises with the host or copies from it: the steps are enqueued back to back.  ``step_xyz`` / ``step_rot`` are
+        starting values that the halving adapts.  A view whose log-likelihood at ``cameras0`` is -inf (a code outside [0, n_embeddings))
+        or NaN never takes a candidate (-inf > -inf is false): it keeps ``cameras0`` and only halves its steps.  -> dict of
+            cameras                 fp32  [B,N,7]  the refined cameras, in the cache's frame
+            log_likelihood          fp32  [B,N]    there: never below ...
+            initial_log_likelihood  fp32  [B,N]    ... the one at ``cameras0``
+            accepted                int32 [B,N]    how many of the ``steps`` proposals each view took
+        and with ``return_trace`` ``trace`` fp32 [steps+1,B,N], the log-likelihood after every step (non-decreasing)."""
+        from .render import ascend_poses
+        if not isinstance(cache, ContextCache):
+            raise TypeError('refine_from_context: a ContextCache from prefill_context expected')
+        if isinstance(steps, bool) or int(steps) != steps or int(steps) < 0:
+            raise ValueError(f'refine_from_context: steps, an integer >= 0, expected, got {steps}')
+        if not (float(step_xyz) > 0 and float(step_rot) > 0 and math.isfinite(float(step_xyz)) and math.isfinite(float(step_rot))):
+            raise ValueError(f'refine_from_context: positive finite step_xyz and step_rot expected, got {step_xyz} and {step_rot}')
+        B = cache.B
+        p, codes, N, ctx = self._score_grad_args('refine_from_context', cache, cameras0, codes, n_context)
+        r = self._score_grad(cache, p, codes, N, ctx)
+        ll, g = r['log_likelihood'], r['grad_cameras']
+        ll0 = ll.clone()
+        s_xyz = torch.full((B, N), float(step_xyz), dtype=torch.float32, device=self.device)
+        s_rot = torch.full((B, N), float(step_rot), dtype=torch.float32, device=self.device)
+        accepted = torch.zeros((B, N), dtype=torch.int32, device=self.device)
+        trace = [ll]
+        for _ in range(int(steps) if N else 0):
+            cand = ascend_poses(p, g, s_xyz, s_rot)
+            rc = self._score_grad(cache, cand, codes, N, ctx)
+            up = rc['log_likelihood'] > ll                                   # (a NaN never wins)
+            up7 = up.unsqueeze(-1)
+            p, g = torch.where(up7, cand, p), torch.where(up7, rc['grad_cameras'], g)
+            ll = torch.where(up, rc['log_likelihood'], ll)
+            s_xyz, s_rot = torch.where(up, s_xyz, s_xyz * 0.5), torch.where(up, s_rot, s_rot * 0.5)
+            accepted = accepted + up.to(torch.int32)
+            trace.append(ll)
+        res = dict(cameras=p, log_likelihood=ll, initial_log_likelihood=ll0, accepted=accepted)
+        if return_trace:
+            res['trace'] = torch.stack(trace + [ll] * (int(steps) + 1 - len(trace)), 0)
+        return res
 
     def sample_from_context(self, cache, query_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                             seed: int = 0, view0: int = 0, return_logits: bool = False, n_context=None):

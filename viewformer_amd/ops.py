@@ -624,6 +624,24 @@ def attn_prefix(q, k, v, kp, vp, out, B, H, C, N, L, ldq, ldk, ldv, ldkp, ldvp, 
     return out
 
 
+def attn_prefix_bwd(q, k, v, kp, vp, dout, dqkv, B, H, C, N, L, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, lddo, lddqkv, dh=64, ctx_len=None):
+    """Backward of ``attn_prefix`` over the query views (csrc/attention_prefix_bwd.hip): q / k / v / kp / vp / ctx_len as there (bf16 or
+    fp32 tensors, one dtype for all five; widened to fp32 on load, fp32 MFMA on either arm), ``dout`` fp32 [B*N*L][lddo] the gradient of
+    the attention output -> ``dqkv`` fp32 [B*N*L][lddqkv] in the c_attn column order (V, Q, K): dV and dK of each view's own keys, dQ.
+    The cache receives no gradient.  Every logical element of ``dqkv`` is written."""
+    lib = _lib.load()
+    if ctx_len is not None:
+        _chk(ctx_len, torch.int32, 'ctx_len')
+        if ctx_len.numel() != B * N or not ctx_len.is_contiguous():
+            raise ValueError(f'attn_prefix_bwd: ctx_len int32 [B*N = {B * N}] contiguous expected, got {tuple(ctx_len.shape)}')
+    i16 = q.dtype == torch.bfloat16
+    for t in (q, k, v, kp, vp):
+        _chk(t, torch.bfloat16 if i16 else torch.float32, 'q/k/v/prefix')
+    check(lib.vf_attn_prefix_bwd_f32(_p(q), _p(k), _p(v), _p(kp), _p(vp), 1 if i16 else 0, _p(_f32(dout)), _p(_f32(dqkv)), B, H, C, N, L, dh,
+                                     ldq, ldk, ldv, ldkp, ldvp, prefix_stride, lddo, lddqkv, _p(ctx_len), _stream()), 'vf_attn_prefix_bwd_f32')
+    return dqkv
+
+
 def kv_append(qkv, cache, B, K, L, d, ld_src, ld_dst, cache_stride, capacity, pos):
     """Append the keys and values of K new views per scene to a context cache with room (csrc/kv_append.hip): ``qkv`` = the new views'
     fused c_attn output, rows [B*K*L] of leading dimension ``ld_src``, thirds (V, Q, K); the V and K thirds of new view j of scene b go

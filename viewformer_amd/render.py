@@ -72,6 +72,40 @@ def query_poses(query_cameras, transform):
     return geometry.normalize_cameras(query_cameras)
 
 
+def ascend_poses(poses, grad, step_xyz, step_rot):
+    """One ascent step on model poses [...,7] (position, unit quaternion) along a gradient [...,7] w.r.t. the 7 numbers taken as free:
+    position + step_xyz * g_xyz / ||g_xyz||; quaternion + step_rot * t / ||t|| with t the part of g_q tangent to the unit sphere at q
+    (g_q - (g_q . q) q: the radial part changes nothing, the model input is read after normalisation by every caller), then
+    renormalised and sign-removed as ``normalize_cameras`` does.  A zero (or non-finite) block does not move, nor does a quaternion whose
+    gradient is radial (tangent part below 1e-6 of it).  ``step_*``: a number or a
+    tensor broadcastable to ``poses[..., 0]``.  Pure torch on [...,7] tensors: no model, no launch of the library."""
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    grad = torch.as_tensor(grad, dtype=torch.float32).to(poses.device)
+    if poses.shape != grad.shape or poses.shape[-1] != 7:
+        raise ValueError(f'ascend_poses: poses and grad [...,7] of one shape expected, got {tuple(poses.shape)} and {tuple(grad.shape)}')
+
+    def step(x):                                                     # a number fills a tensor on the device (no copy from the host)
+        if isinstance(x, torch.Tensor):
+            return x.to(device=poses.device, dtype=torch.float32).expand(poses.shape[:-1]).unsqueeze(-1)
+        return torch.full((*poses.shape[:-1], 1), float(x), dtype=torch.float32, device=poses.device)
+
+    sx, sr = step(step_xyz), step(step_rot)
+
+    def unit(v, floor=0.0):
+        n = v.norm(dim=-1, keepdim=True)
+        ok = torch.isfinite(n) & (n > floor)
+        return torch.where(ok, v / torch.where(ok, n, torch.ones_like(n)), torch.zeros_like(v))
+
+    q = geometry.quaternion_normalize(poses[..., 3:])
+    gq = grad[..., 3:]
+    tangent = gq - (gq * q).sum(-1, keepdim=True) * q
+    xyz = poses[..., :3] + sx * unit(grad[..., :3])
+    ut = unit(tangent, floor=1e-6 * gq.norm(dim=-1, keepdim=True))       # a purely radial g_q leaves rounding noise, not a direction
+    moved = (ut != 0).any(-1, keepdim=True)
+    quat = geometry.quaternion_remove_sign(geometry.quaternion_normalize(q + sr * ut))
+    return torch.cat((xyz, torch.where(moved, quat, poses[..., 3:])), -1)
+
+
 def default_views_per_call(n_scenes: int) -> int:
     """Query views per scene in one transformer pass: at most MAX_SCENES_PER_CALL view-rows over the batch, the evaluator's own cap
     (one query view has the activations of one of its scenes' views; the cap keeps every activation below 32-bit offsets)."""
@@ -472,6 +506,89 @@ class ViewRenderer:
             parts = [tm.score_from_context(self.cache, poses, codes[:, :0], **kw)]      # N = 0: empty tensors of the right shapes
         return {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
 
+    def _photo_codes(self, what, images, codes, N):
+        """``images`` uint8 [B,N or 1,H,W,3] or ``codes`` int [B,N or 1,t,t] (exactly one) -> int32 codes [B,P,t,t], P in (1, N); N None: any P"""
+        if (images is None) == (codes is None):
+            raise ValueError(f'{what}: exactly one of images / codes expected')
+        tm, cm = self.transformer, self.codebook
+        dev, B, t = cm.device, self.cache.B, tm.config.token_image_size
+        views = f'N={N} or 1' if N is not None else 'N'
+        if codes is None:
+            images = torch.as_tensor(images).to(dev)
+            if images.dim() != 5 or images.shape[0] != B or (N is not None and images.shape[1] not in (1, N)):
+                raise ValueError(f'{what}: images [B={B},{views},H,W,3] expected, got {tuple(images.shape)}')
+            P = images.shape[1]
+            codes = (cm.encode(_frames_for_encode(images, cm.config.image_size))[-1] if P
+                     else torch.empty((B, 0, t, t), dtype=torch.int32, device=dev))
+        else:
+            codes = torch.as_tensor(codes).to(dev)
+            if (codes.dim() != 4 or codes.shape[0] != B or (N is not None and codes.shape[1] not in (1, N)) or tuple(codes.shape[2:]) != (t, t)
+                    or codes.dtype.is_floating_point or codes.dtype == torch.bool):
+                raise ValueError(f'{what}: codes int [B={B},{views},{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
+            P = codes.shape[1]
+        return codes.to(torch.int32).view(B, P, t, t)
+
+    def _world_cameras(self, what, cameras):
+        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.codebook.device)
+        if cameras.dim() != 3 or cameras.shape[0] != self.cache.B or cameras.shape[-1] != 7:
+            raise ValueError(f'{what}: cameras [B={self.cache.B},N,7] expected, got {tuple(cameras.shape)}')
+        return cameras
+
+    def score_gradient(self, query_cameras, images=None, codes=None, max_views_per_call: int = None, n_context=None):
+        """``score`` plus which way each camera should move: ``MIGT.score_grad_from_context``'s dict (``score``'s keys with the same
+        bits, and grad_cameras fp32 [B,N,7]) plus ``poses`` fp32 [B,N,7], the MODEL-frame cameras (relative to context view 0 where the
+        model was trained so, normalised) that the gradient refers to: grad_cameras[b,n] = d log_likelihood[b,n] / d poses[b,n].
+        Arguments as ``score``'s; N is walked in chunks of whole views (``plan_view_chunks``), a view's result does not depend on the
+        chunking."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.score_gradient: set_context() first')
+        query_cameras = self._world_cameras('score_gradient', query_cameras)
+        B, N = self.cache.B, query_cameras.shape[1]
+        codes = self._photo_codes('score_gradient', images, codes, N)
+        poses = query_poses(query_cameras, self.transform)
+        one = codes.shape[1] == 1 and N != 1
+        lens = self._lengths(n_context, N)
+        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
+        tm = self.transformer
+        parts = [tm.score_grad_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **lkw(a, b))
+                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
+        if not parts:
+            parts = [tm.score_grad_from_context(self.cache, poses, codes[:, :0])]      # N = 0: empty tensors of the right shapes
+        res = {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        res['poses'] = poses
+        return res
+
+    def refine(self, cameras0=None, images=None, codes=None, steps: int = 16, step_xyz: float = 0.05, step_rot: float = 0.05,
+               max_views_per_call: int = None, n_context=None, return_trace: bool = False):
+        """Refine camera estimates of N photos per scene by gradient ascent on their log-likelihood (``MIGT.refine_from_context``):
+        ``cameras0`` [B,N,7] in the caller's world frame, or None to start from ``self.localize(...)`` of the same photos; ``images`` /
+        ``codes`` as ``score``'s -> dict(generated_cameras fp32 [B,N,7] in the world frame, through ``from_relative_cameras`` as
+        ``localize``; cameras [B,N,7] in the model's frame; log_likelihood, initial_log_likelihood fp32 [B,N]; accepted int32 [B,N]; with
+        ``return_trace`` trace fp32 [steps+1,B,N]).  N is walked in chunks of whole views; views are refined independently of each other."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.refine: set_context() first')
+        B = self.cache.B
+        if cameras0 is not None:
+            cameras0 = self._world_cameras('refine', cameras0)
+        codes = self._photo_codes('refine', images, codes, None if cameras0 is None else cameras0.shape[1])
+        if cameras0 is None:
+            cameras0 = self.localize(codes=codes, max_views_per_call=max_views_per_call, n_context=n_context)['generated_cameras']
+        N = cameras0.shape[1]
+        poses = query_poses(cameras0, self.transform)
+        one = codes.shape[1] == 1 and N != 1
+        lens = self._lengths(n_context, N)
+        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
+        kw = dict(steps=steps, step_xyz=step_xyz, step_rot=step_rot, return_trace=return_trace)
+        tm = self.transformer
+        parts = [tm.refine_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **kw, **lkw(a, b))
+                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
+        if not parts:
+            parts = [tm.refine_from_context(self.cache, poses, codes[:, :0], **kw)]
+        res = {k: (torch.cat([p[k] for p in parts], 2 if k == 'trace' else 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        cams = res['cameras']
+        res['generated_cameras'] = geometry.from_relative_cameras(cams, self.transform) if self.transform is not None else cams
+        return res
+
     def localize(self, images=None, codes=None, max_views_per_call: int = None, return_tokens: bool = False, n_context=None):
         """Estimate the cameras of N photos per scene against the context: ``images`` uint8 [B,N,H,W,3] (host or device; resized for
         the encoder as the evaluators do, each photo encoded once) or ``codes`` int [B,N,t,t] (already encoded, e.g.
@@ -616,6 +733,14 @@ def score_views(transformer_model, codebook_model, images, cameras, query_camera
     (the photos' codes instead of ``photos``), ``max_views_per_call``."""
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
     return r.score(query_cameras, images=photos, codes=kw.pop('photo_codes', None), **kw)
+
+
+def refine_views(transformer_model, codebook_model, images, cameras, photos=None, cameras0=None, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7], ``photos`` uint8 [B,N,H,W,3] and ``cameras0`` [B,N,7] (None:
+    the localizer's estimate) -> ``ViewRenderer.refine``'s dict.  Keywords: ``codes`` (context codes instead of images; pass images=None),
+    ``photo_codes`` (the photos' codes instead of ``photos``), ``steps``, ``step_xyz``, ``step_rot``, ``max_views_per_call``, ``return_trace``."""
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    return r.refine(cameras0, images=photos, codes=kw.pop('photo_codes', None), **kw)
 
 
 def localize_views(transformer_model, codebook_model, images, cameras, photos=None, **kw):
