@@ -307,6 +307,34 @@ int vf_attn_prefix_var_bf16(const void* q, const void* k, const void* v, const v
 int vf_attn_prefix_var_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
                              int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                              int ldo, const int32_t* ctx_len, void* stream);
+/* The same two kernels over a FORKED cache (ContextCache.fork): the context of child scene b is a SHARED segment, the leading views of
+ * parent scene b / share read where they lie, followed by an OWN segment that only this child has.  B counts child scenes.
+ *   parent segment: kp, vp, ldkp, ldvp, prefix_stride, C as above, addressed by scene b / share (share >= 1; the caller provides
+ *                   (B - 1) / share + 1 parent scenes);
+ *   own segment:    kp2, vp2, ldkp2, ldvp2, prefix_stride2, addressed by scene b, C2 >= 0 views of room per scene; with C2 = 0 the own
+ *                   segment is never read and kp2 / vp2 may be NULL;
+ *   split:          DEVICE pointer to [B] int32: logical view s of scene b is parent view s if s < split[b], else own view s - split[b];
+ *   ctx_len:        DEVICE pointer to [B*N] int32, counting LOGICAL views.
+ * split is clamped to [0, C] on read and a length to [0, split + C2]: no value of either array takes a load outside either buffer.  All
+ * views of a workgroup belong to one scene, so the segment of a step is uniform in it; staging, grouping, the key order (parent views
+ * ascending, own views ascending, then the view's own tile) and the arithmetic are those of vf_attn_prefix_var_*.  Contract:
+ *   1. a view gets exactly the bits that vf_attn_prefix_var_* gives it on the MATERIALISED cache of its scene — the parent's first split[b]
+ *      views followed by the own views, contiguous — whatever N, its position, its neighbours' lengths, or share;
+ *   2. with share = 1, split[b] = C and C2 = 0 the entry is the VAR entry;
+ *   3. parent rows at or beyond split[b], own rows at or beyond len - split[b], and every row of another scene's own segment do not reach
+ *      a view's result;
+ *   4. the kernel writes exactly the logical output elements.
+ * Checks as vf_attn_prefix_var_* (L != 64, dh != 64, C < 1: VF_ERR_UNSUPPORTED), and NULL split, NULL kp2 / vp2 with C2 > 0, share < 1,
+ * C2 < 0, ldkp2 / ldvp2 < H * 64, or ldkp2 / ldvp2 / prefix_stride2 misaligned (% 8 bf16, % 4 fp32; checked whatever C2) or
+ * prefix_stride2 < 0: VF_ERR_BAD_ARG; all before any launch.  B = 0 or N = 0: no-op, VF_OK. */
+int vf_attn_prefix_fork_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
+                             int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                             int ldo, const int32_t* ctx_len, const void* kp2, const void* vp2, int C2, int ldkp2, int ldvp2,
+                             int64_t prefix_stride2, const int32_t* split, int share, void* stream);
+int vf_attn_prefix_fork_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
+                              int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                              int ldo, const int32_t* ctx_len, const float* kp2, const float* vp2, int C2, int ldkp2, int ldvp2,
+                              int64_t prefix_stride2, const int32_t* split, int share, void* stream);
 /* Backward of the prefix-cache attention over the QUERY views (csrc/attention_prefix_bwd.hip; MIGT.score_grad_from_context): the inputs of
  * vf_attn_prefix_var_* — q / k / v, the query views' thirds of the fused c_attn output, rows [B*N*L]; kp / vp, the cache with ld*,
  * prefix_stride and capacity C; ctx_len, a device pointer to [B*N] int32 (clamped to [0, C] on read) or NULL for "all C views" — plus

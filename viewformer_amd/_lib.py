@@ -103,6 +103,9 @@ EXPORTS = {
     'vf_attn_prefix_f32eq': (c_int, [P, P, P, P, P, P] + [c_int] * 11 + [c_int64, c_int, P]),
     'vf_attn_prefix_var_bf16': (c_int, [P, P, P, P, P, c_int, P, c_int] + [c_int] * 11 + [c_int64, c_int, P, P]),
     'vf_attn_prefix_var_f32eq': (c_int, [P, P, P, P, P, P] + [c_int] * 11 + [c_int64, c_int, P, P]),
+    'vf_attn_prefix_fork_bf16': (c_int, [P, P, P, P, P, c_int, P, c_int] + [c_int] * 11 + [c_int64, c_int, P,
+                                         P, P, c_int, c_int, c_int, c_int64, P, c_int, P]),
+    'vf_attn_prefix_fork_f32eq': (c_int, [P, P, P, P, P, P] + [c_int] * 11 + [c_int64, c_int, P, P, P, c_int, c_int, c_int, c_int64, P, c_int, P]),
     'vf_attn_prefix_bwd_f32': (c_int, [P, P, P, P, P, c_int, P, P] + [c_int] * 11 + [c_int64, c_int, c_int, P, P]),
     'vf_kv_append': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, P, P]),
     'vf_attn_blockcausal_lse_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

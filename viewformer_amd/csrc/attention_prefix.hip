@@ -24,6 +24,15 @@
 //   - the kernel writes exactly the logical output elements;
 //   - a view's result does not depend on cache rows at or beyond its length.
 // The fixed-C instantiation compiles to what it was (gmax = mylen = C are the same value): same bits, same registers.
+//
+// Forked caches (vf_attn_prefix_fork_*, the kernels' FORK instantiation): the logical context of child scene b is the first split[b] views of
+// PARENT scene b / share (kp / vp, read where they lie) followed by the scene's OWN views (kp2 / vp2, addressed by b).  Lengths count logical
+// views and work as in VAR; split is clamped to [0, C] and a length to [0, split + C2] on read, so no value of either array takes a load
+// outside either buffer (own view s - split < C2 whenever it is read; with C2 = 0 the own segment is never read).  All views of a workgroup
+// belong to one scene, so the segment of step s — and with it the base pointer, leading dimension and view number in prefetch(s) — is uniform
+// in the workgroup.  Staging, the group logic, the key order (parent ascending, own ascending, the view's own tile) and the arithmetic are
+// those of VAR: a view gets the bits that VAR gives it on the materialised cache (parent views [0, split) and the own views, contiguous).
+// The fixed-C and VAR instantiations take prefix_args as before and compile to what they were.
 #include "vf_common.h"
 #include "../../include/vf_hip.h"
 
@@ -46,13 +55,26 @@ struct prefix_args {
     int ldq, ldk, ldv, ldkp, ldvp, ldo;
     long long pstride;
     int in16, out16;
-    const int* ctx_len;                               // VAR only: [B*N] context lengths, one per query view
+    const int* ctx_len;                               // VAR / FORK: [B*N] context lengths, one per query view
 };
 
-// VAR: the length of query view (b, n), clamped to the cache's capacity; fixed-C: C
-template <bool VAR>
-__device__ __forceinline__ int view_len(const prefix_args& a, size_t b, int n) {
-    if constexpr (VAR) return min(max(a.ctx_len[b * (size_t)a.N + (size_t)n], 0), a.C);
+// FORK: the second (own) segment and the mapping; B counts CHILD scenes
+struct fork_args : prefix_args {
+    const void* kp2; const void* vp2;                 // own K / V, rows [C2*L] per child scene, scenes pstride2 elements apart
+    int C2, share;                                    // room of the own segment in views; child scene b reads parent scene b / share
+    int ldkp2, ldvp2;
+    long long pstride2;
+    const int* split;                                 // [B]: logical view s of scene b is parent view s if s < split[b], else own view s - split[b]
+};
+
+enum { FIXED = 0, VAR = 1, FORK = 2 };
+template <int MODE> struct args_of { typedef prefix_args type; };
+template <> struct args_of<FORK> { typedef fork_args type; };
+
+// VAR / FORK: the length of query view (b, n), clamped to the room (VAR: the cache's capacity; FORK: the scene's split + the own room); fixed-C: C
+template <int MODE>
+__device__ __forceinline__ int view_len(const prefix_args& a, size_t b, int n, int room) {
+    if constexpr (MODE != FIXED) return min(max(a.ctx_len[b * (size_t)a.N + (size_t)n], 0), room);
     else return a.C;
 }
 
@@ -68,8 +90,8 @@ __device__ __forceinline__ f32x4 load4(const void* base, size_t off, int in16) {
 constexpr int K_LDB = 144;            // K row [key][dh] bf16: 128 B + 16 (conflict-free ds_read_b128)
 constexpr int VT_LDB = 136;           // V^T row [feature][key] bf16: 128 B + 8
 
-template <bool VAR>
-__global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const prefix_args a) {
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const typename args_of<MODE>::type a) {
     __shared__ __attribute__((aligned(16))) unsigned char Ks[LV * K_LDB];
     __shared__ __attribute__((aligned(16))) unsigned char Vt[DH * VT_LDB];
 
@@ -105,10 +127,18 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const prefix_a
     // VAR: the wave walks its own view's first mylen prefix tiles; the group stages gmax = its longest member's (a wave without a view
     // counts as length 0 and reads no length)
     int mylen = a.C, gmax = a.C;
-    if constexpr (VAR) {
+    int split = a.C;                                             // FORK: the scene's first own view (parent views below it), uniform in the workgroup
+    size_t pscene = b;                                           // the scene of the kp / vp segment
+    if constexpr (MODE != FIXED) {
+        int room = a.C;
+        if constexpr (MODE == FORK) {
+            split = min(max(a.split[b], 0), a.C);
+            room = split + a.C2;
+            pscene = b / (size_t)a.share;
+        }
         gmax = 0;
-        for (int j = 0; j < nown; ++j) gmax = max(gmax, view_len<VAR>(a, b, v0 + j));
-        mylen = active ? view_len<VAR>(a, b, v0 + wave) : 0;
+        for (int j = 0; j < nown; ++j) gmax = max(gmax, view_len<MODE>(a, b, v0 + j, room));
+        mylen = active ? view_len<MODE>(a, b, v0 + wave, room) : 0;
     }
     const int nsteps = gmax + nown;                              // gmax prefix tiles, then the group's own tiles
     f32x4 kreg[4], vreg[4];
@@ -116,10 +146,18 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const prefix_a
         const void *kb, *vb;
         size_t k0, v0_;
         int ldk_, ldv_;
-        if (s < gmax) {
+        bool own2 = false;
+        if constexpr (MODE == FORK) own2 = s >= split && s < gmax;
+        if (own2) {
+            if constexpr (MODE == FORK) {                            // own view s - split < C2 of child scene b
+                kb = a.kp2; vb = a.vp2; ldk_ = a.ldkp2; ldv_ = a.ldvp2;
+                k0 = b * (size_t)a.pstride2 + (size_t)(s - split) * LV * ldk_ + h * DH;
+                v0_ = b * (size_t)a.pstride2 + (size_t)(s - split) * LV * ldv_ + h * DH;
+            }
+        } else if (s < gmax) {
             kb = a.kp; vb = a.vp; ldk_ = a.ldkp; ldv_ = a.ldvp;
-            k0 = b * (size_t)a.pstride + (size_t)s * LV * ldk_ + h * DH;
-            v0_ = b * (size_t)a.pstride + (size_t)s * LV * ldv_ + h * DH;
+            k0 = pscene * (size_t)a.pstride + (size_t)s * LV * ldk_ + h * DH;
+            v0_ = pscene * (size_t)a.pstride + (size_t)s * LV * ldv_ + h * DH;
         } else {
             kb = a.k; vb = a.v; ldk_ = a.ldk; ldv_ = a.ldv;
             const size_t r0 = (b * (size_t)a.N + (size_t)(v0 + s - gmax)) * LV;
@@ -279,8 +317,8 @@ __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l)
 constexpr int K6_LDB = 400;   // bytes per K row in LDS: 3 planes x 128 B + 16 B pad (attention_x6.hip)
 constexpr int VT6_LDB = 392;  // bytes per V^T row: 3 planes x 128 B + 8 B pad
 
-template <bool VAR>
-__global__ __launch_bounds__(256, 2) void attn_prefix_x6_kernel(const prefix_args a) {
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void attn_prefix_x6_kernel(const typename args_of<MODE>::type a) {
     __shared__ __attribute__((aligned(16))) unsigned char Ks[LV * K6_LDB];
     __shared__ __attribute__((aligned(16))) unsigned char Vt[DH * VT6_LDB];
 
@@ -320,20 +358,36 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_x6_kernel(const prefix_arg
     const int s_col4 = tid & 15;
     const int s_row0 = tid >> 4;
     int mylen = a.C, gmax = a.C;                                 // as the bf16 arm
-    if constexpr (VAR) {
+    int split = a.C;
+    size_t pscene = b;
+    if constexpr (MODE != FIXED) {
+        int room = a.C;
+        if constexpr (MODE == FORK) {
+            split = min(max(a.split[b], 0), a.C);
+            room = split + a.C2;
+            pscene = b / (size_t)a.share;
+        }
         gmax = 0;
-        for (int j = 0; j < nown; ++j) gmax = max(gmax, view_len<VAR>(a, b, v0 + j));
-        mylen = active ? view_len<VAR>(a, b, v0 + slot) : 0;
+        for (int j = 0; j < nown; ++j) gmax = max(gmax, view_len<MODE>(a, b, v0 + j, room));
+        mylen = active ? view_len<MODE>(a, b, v0 + slot, room) : 0;
     }
     const int nsteps = gmax + nown;
     f32x4 kreg[4], vreg[4];
     auto prefetch = [&](int s) {
         const float *kb, *vb;
         int ldk_, ldv_;
-        if (s < gmax) {
+        bool own2 = false;
+        if constexpr (MODE == FORK) own2 = s >= split && s < gmax;
+        if (own2) {
+            if constexpr (MODE == FORK) {                            // own view s - split < C2 of child scene b
+                ldk_ = a.ldkp2; ldv_ = a.ldvp2;
+                kb = reinterpret_cast<const float*>(a.kp2) + b * (size_t)a.pstride2 + (size_t)(s - split) * LV * ldk_ + h * DH;
+                vb = reinterpret_cast<const float*>(a.vp2) + b * (size_t)a.pstride2 + (size_t)(s - split) * LV * ldv_ + h * DH;
+            }
+        } else if (s < gmax) {
             ldk_ = a.ldkp; ldv_ = a.ldvp;
-            kb = reinterpret_cast<const float*>(a.kp) + b * (size_t)a.pstride + (size_t)s * LV * ldk_ + h * DH;
-            vb = reinterpret_cast<const float*>(a.vp) + b * (size_t)a.pstride + (size_t)s * LV * ldv_ + h * DH;
+            kb = reinterpret_cast<const float*>(a.kp) + pscene * (size_t)a.pstride + (size_t)s * LV * ldk_ + h * DH;
+            vb = reinterpret_cast<const float*>(a.vp) + pscene * (size_t)a.pstride + (size_t)s * LV * ldv_ + h * DH;
         } else {
             ldk_ = a.ldk; ldv_ = a.ldv;
             const size_t r0 = (b * (size_t)a.N + (size_t)(v0 + s - gmax)) * LV;
@@ -505,25 +559,42 @@ int prefix_check(const prefix_args& a, int B, int H, int L, int dh) {
     return VF_OK;
 }
 
-template <bool VAR>
-int launch_bf16(const prefix_args& a, int B, int H, int L, int dh, void* stream) {
-    if (VAR && !a.ctx_len) return VF_ERR_BAD_ARG;
-    const int rc = prefix_check(a, B, H, L, dh);
+// the own segment and the mapping of a fork (host only); B = 0 / N = 0 are no-ops AFTER these checks, as everywhere
+int fork_check(const fork_args& a, int H) {
+    if (!a.split || a.share < 1 || a.C2 < 0) return VF_ERR_BAD_ARG;
+    if (a.C2 > 0 && (!a.kp2 || !a.vp2)) return VF_ERR_BAD_ARG;   // C2 = 0: the own segment is never read, its pointers may be NULL
+    if (a.ldkp2 < H * DH || a.ldvp2 < H * DH) return VF_ERR_BAD_ARG;
+    const long long al = a.in16 ? 7 : 3;
+    if (((long long)(a.ldkp2 | a.ldvp2) | a.pstride2) & al) return VF_ERR_BAD_ARG;
+    if (a.pstride2 < 0) return VF_ERR_BAD_ARG;
+    return VF_OK;
+}
+
+template <int MODE>
+int launch_bf16(const typename args_of<MODE>::type& a, int B, int H, int L, int dh, void* stream) {
+    if (MODE != FIXED && !a.ctx_len) return VF_ERR_BAD_ARG;
+    int rc = prefix_check(a, B, H, L, dh);
+    if constexpr (MODE == FORK) {
+        if (rc == VF_OK) rc = fork_check(a, H);
+    }
     if (rc != VF_OK) return rc;
     if (B == 0 || a.N == 0) return VF_OK;
     dim3 grid((unsigned)H, (unsigned)B, (unsigned)((a.N + GV16 - 1) / GV16));
-    hipLaunchKernelGGL(attn_prefix_bf16_kernel<VAR>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(attn_prefix_bf16_kernel<MODE>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return vf_last_status();
 }
 
-template <bool VAR>
-int launch_x6(const prefix_args& a, int B, int H, int L, int dh, void* stream) {
-    if (VAR && !a.ctx_len) return VF_ERR_BAD_ARG;
-    const int rc = prefix_check(a, B, H, L, dh);
+template <int MODE>
+int launch_x6(const typename args_of<MODE>::type& a, int B, int H, int L, int dh, void* stream) {
+    if (MODE != FIXED && !a.ctx_len) return VF_ERR_BAD_ARG;
+    int rc = prefix_check(a, B, H, L, dh);
+    if constexpr (MODE == FORK) {
+        if (rc == VF_OK) rc = fork_check(a, H);
+    }
     if (rc != VF_OK) return rc;
     if (B == 0 || a.N == 0) return VF_OK;
     dim3 grid((unsigned)H, (unsigned)B, (unsigned)((a.N + GV32 - 1) / GV32));
-    hipLaunchKernelGGL(attn_prefix_x6_kernel<VAR>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(attn_prefix_x6_kernel<MODE>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return vf_last_status();
 }
 
@@ -536,14 +607,14 @@ int vf_attn_prefix_bf16(const void* q, const void* k, const void* v, const void*
                         int ldo, void* stream) {
     const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0,
                         nullptr};
-    return launch_bf16<false>(a, B, H, L, dh, stream);
+    return launch_bf16<FIXED>(a, B, H, L, dh, stream);
 }
 
 int vf_attn_prefix_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
                          int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                          int ldo, void* stream) {
     const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, 0, 0, nullptr};
-    return launch_x6<false>(a, B, H, L, dh, stream);
+    return launch_x6<FIXED>(a, B, H, L, dh, stream);
 }
 
 int vf_attn_prefix_var_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
@@ -551,14 +622,32 @@ int vf_attn_prefix_var_bf16(const void* q, const void* k, const void* v, const v
                             int ldo, const int32_t* ctx_len, void* stream) {
     const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0,
                         ctx_len};
-    return launch_bf16<true>(a, B, H, L, dh, stream);
+    return launch_bf16<VAR>(a, B, H, L, dh, stream);
 }
 
 int vf_attn_prefix_var_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
                              int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                              int ldo, const int32_t* ctx_len, void* stream) {
     const prefix_args a{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, 0, 0, ctx_len};
-    return launch_x6<true>(a, B, H, L, dh, stream);
+    return launch_x6<VAR>(a, B, H, L, dh, stream);
+}
+
+int vf_attn_prefix_fork_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
+                             int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                             int ldo, const int32_t* ctx_len, const void* kp2, const void* vp2, int C2, int ldkp2, int ldvp2,
+                             int64_t prefix_stride2, const int32_t* split, int share, void* stream) {
+    const fork_args a{{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0,
+                       ctx_len}, kp2, vp2, C2, share, ldkp2, ldvp2, (long long)prefix_stride2, split};
+    return launch_bf16<FORK>(a, B, H, L, dh, stream);
+}
+
+int vf_attn_prefix_fork_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,
+                              int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
+                              int ldo, const int32_t* ctx_len, const float* kp2, const float* vp2, int C2, int ldkp2, int ldvp2,
+                              int64_t prefix_stride2, const int32_t* split, int share, void* stream) {
+    const fork_args a{{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, 0, 0, ctx_len},
+                      kp2, vp2, C2, share, ldkp2, ldvp2, (long long)prefix_stride2, split};
+    return launch_x6<FORK>(a, B, H, L, dh, stream);
 }
 
 }  // extern "C"

@@ -34,11 +34,22 @@ class ContextCache:
     """Keys and values of C context views in every layer (MIGT.prefill_context): ``kv[i]`` is layer i's fused c_attn output
     [B*capacity*L, 3*d_model] with thirds (V, Q, K).  Valid for the model object, weights, arithmetic arm and device that made it.
     ``capacity`` >= C views of room per scene (``prefill_context(capacity=...)``, grown by ``append_to_context``); ``C`` = the number of
-    filled views, the maximum over scenes; ``lengths``: the filled views per scene, host int32 [B], or None for "all C"."""
-    __slots__ = ('kv', 'B', 'C', 'tshape', 'device', 'arm', 'act16', 'qkv16', '_owner', '_weights', 'capacity', 'lengths')
+    filled views, the maximum over scenes; ``lengths``: the filled views per scene, host int32 [B], or None for "all C".
+
+    A FORKED cache (``fork(S)``) has B*S scenes that read the parent's views where they lie and own only what they add:
+    ``parent_kv`` = the parent's per-layer tensors as they were at fork time (a list of its own: a parent that reallocates later keeps
+    the old buffers alive for the child), ``parent_capacity`` their views of room per scene, ``split`` host int32 [B*S] = the parent's
+    filled length per child scene at fork time, ``share`` = S (child scene b reads parent scene b // S), ``room`` = own views of room
+    per child scene, and ``kv[i]`` the OWN buffers [B*S*room*L, 3*d_model].  ``filled()``, ``lengths``, ``C`` and ``capacity`` count
+    LOGICAL views: logical view s of scene b is parent view s below ``split[b]``, own view ``s - split[b]`` otherwise
+    (``render.map_fork_views``).  Every child holds the same number of own views."""
+    _FIELDS = ('kv', 'B', 'C', 'tshape', 'device', 'arm', 'act16', 'qkv16', '_owner', '_weights', 'capacity', 'lengths',
+               'parent_kv', 'parent_capacity', 'split', 'share', 'room', '_parent', '_split_dev')
+    __slots__ = _FIELDS + ('__weakref__',)
 
     def __init__(self, model, kv, B, C, tshape, capacity=None, lengths=None):
         import weakref
+        self.parent_kv = self.parent_capacity = self.split = self.share = self.room = self._parent = self._split_dev = None
         self.kv, self.B, self.C, self.tshape = kv, B, C, tuple(tshape)
         self.capacity = C if capacity is None else int(capacity)
         self.lengths = None if lengths is None else np.array(lengths, dtype=np.int32).reshape(B)
@@ -60,11 +71,39 @@ class ContextCache:
         """A second ContextCache on the SAME buffers with lengths of its own: what is appended through it lies beyond this cache's lengths
         (and moves to new buffers, leaving these, once the capacity is exceeded)."""
         c = object.__new__(ContextCache)
-        for s in self.__slots__:
+        for s in self._FIELDS:
             setattr(c, s, getattr(self, s))
         c.kv = list(self.kv)
         c.lengths = None if self.lengths is None else self.lengths.copy()
+        if self.forked():
+            c.parent_kv = list(self.parent_kv)
         return c
+
+    def forked(self):
+        """True for a cache made by ``fork``: two segments per scene, the parent's and its own"""
+        return self.share is not None
+
+    def _model(self, what):
+        m = self._owner()
+        if m is None:
+            raise ValueError(f'ContextCache.{what}: the model that filled this cache is gone')
+        self.check(m)
+        return m
+
+    def fork(self, S, room=None):
+        """S children per scene that share this cache's views and own only what they add: a forked ContextCache of B*S scenes, scene b's
+        children at b*S ... b*S+S-1 (the order of ``render.plan_replication``), each starting at this cache's filled length of scene b.
+        ``room``: own views of room per child (None: 0, allocated at the first append; grown by doubling, own buffers only).  Nothing of
+        this cache is copied, written or run again, and nothing appended to it later — behind its lengths of now — reaches a child.
+        ``generate`` / ``sample`` / ``score`` / ``localize_from_context``, ``append_to_context`` and ``rollout_from_context`` take the
+        fork as any cache, with the bits of the materialised cache; ``score_grad_from_context`` and ``refine_from_context`` need
+        ``materialize()``.  A fork of a fork is refused: ``materialize()`` it first."""
+        return self._model('fork')._fork(self, S, room)
+
+    def materialize(self):
+        """A plain ContextCache of this fork's B*S scenes in buffers of its own: the parent's views at position 0, the own views behind
+        them, copied bit for bit by ``ops.kv_append`` (every result on it has the fork's bits).  On a plain cache: a copy."""
+        return self._model('materialize')._materialize(self)
 
     def check(self, model):
         if self._owner() is not model or self._weights != model._weights_version:
@@ -382,6 +421,15 @@ class MIGT:
         d, L = self.config.d_model, int(np.prod(cache.tshape))
         B, old = cache.B, cache.capacity
         pos0 = torch.zeros(B, dtype=torch.int32, device=self.device)
+        if cache.forked():                                                   # a fork grows its OWN buffers only: the parent's stay where they lie
+            room = capacity - int(cache.split.max())
+            for i, src in enumerate(cache.kv):
+                dst = torch.empty((B * room * L, 3 * d), dtype=src.dtype, device=self.device)
+                if cache.room:
+                    ops.kv_append(src, dst, B, cache.room, L, d, 3 * d, 3 * d, room * L * 3 * d, room, pos0)
+                cache.kv[i] = dst
+            cache.room, cache.capacity = room, capacity
+            return
         for i, src in enumerate(cache.kv):
             dst = torch.empty((B * capacity * L, 3 * d), dtype=src.dtype, device=self.device)
             ops.kv_append(src, dst, B, old, L, d, 3 * d, 3 * d, capacity * L * 3 * d, capacity, pos0)
@@ -425,7 +473,9 @@ class MIGT:
         ``save``: None (the path and the launches without the keyword), or a list that receives what a backward pass over these rows
         needs (``score_grad_from_context``): per layer the tuple (the block's input h, the residual stream after the attention, the
         layer's fused c_attn output in a buffer of its own, the LayerNorm-2 output), then the final h that ``ln_f`` reads.  Same launches
-        on the same values: the hidden states keep their bits.  With ``tail='all'`` only."""
+        on the same values: the hidden states keep their bits.  With ``tail='all'`` only.
+        A forked cache (``ContextCache.fork``) takes the fork route here and nowhere else: ``ops.attn_prefix_fork`` over the parent's
+        buffers and the own ones, and ``append_at`` (logical) writes the own buffers at ``append_at - split``."""
         c, dev = self.config, self.device
         B, C = cache.B, cache.capacity                                       # the attention's C is the room: lengths say what is filled
         if save is not None and tail != 'all':
@@ -435,6 +485,12 @@ class MIGT:
         M = B * N * L
         if append_at is not None and n_context is None:
             raise ValueError('_query_rows: appended views carry their context lengths')
+        fork = cache.forked()
+        if fork:                                                             # lengths and positions are logical: own view = logical - split
+            if n_context is None:
+                raise ValueError('_query_rows: a forked cache takes the length route')
+            Cp, room = cache.parent_capacity, cache.room
+            own_at = None if append_at is None else append_at - cache._split_dev
         h = ops.embed_sum(ids32, self._wte, self._wpe, add, B * N, L, d, nE + 2)           # migt.py:392
         act16, qkv16 = cache.act16, cache.qkv16
         att = torch.empty((M, d), dtype=torch.bfloat16 if act16 else torch.float32, device=dev)
@@ -449,11 +505,21 @@ class MIGT:
             self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
             ckv = cache.kv[i]                                                # [B*capacity*L, 3d], thirds (V, Q, K)
             if append_at is not None:
-                ops.kv_append(qkv, ckv, B, N, L, d, 3 * d, 3 * d, C * L * 3 * d, C, append_at)
+                if fork:                                                     # ckv: the OWN buffer [B*room*L, 3d]
+                    ops.kv_append(qkv, ckv, B, N, L, d, 3 * d, 3 * d, room * L * 3 * d, room, own_at)
+                else:
+                    ops.kv_append(qkv, ckv, B, N, L, d, 3 * d, 3 * d, C * L * 3 * d, C, append_at)
             if last and tail is None:
                 return None                                                  # the last block's other launches feed nothing: the keys and values are in
-            ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
-                            3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
+            if fork:
+                pkv = cache.parent_kv[i]                                     # [B/share*Cp*L, 3d], read where it lies
+                own = (ckv[:, 2 * d:], ckv[:, :d]) if room else (None, None)
+                ops.attn_prefix_fork(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], pkv[:, 2 * d:], pkv[:, :d], *own, att, B, H, Cp, room, N, L,
+                                     3 * d, 3 * d, 3 * d, 3 * d, 3 * d, Cp * L * 3 * d, 3 * d, 3 * d, room * L * 3 * d, d, n_context,
+                                     cache._split_dev, cache.share, bf16=self.precision == 'bf16')
+            else:
+                ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
+                                3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
             att_i = att
             if last and tail != 'all' and N > 1:
                 # the last block: only the returned view's rows go on (as _blocks' tail_views: the other views' rows feed nothing)
@@ -663,6 +729,8 @@ class MIGT:
         ``_context_lengths`` makes them: None or an int32 device tensor [B*N], planned on the host and copied once)"""
         if not isinstance(cache, ContextCache):
             raise TypeError(f'{what}: a ContextCache from prefill_context expected')
+        if cache.forked():
+            raise ValueError(f'{what}: the backward pass has no fork arm: pass cache.materialize() instead of the forked cache')
         B, tshape = cache.B, cache.tshape
         L = int(np.prod(tshape))
         self._check_render_shapes(L)
@@ -871,7 +939,11 @@ class MIGT:
         """room for ``needed`` views per scene: beyond the capacity, new buffers of max(2 capacity, needed) views (render.plan_capacity)"""
         from .render import plan_capacity
         if needed > cache.capacity:
-            self._reallocate(cache, plan_capacity(cache.capacity, needed))
+            if cache.forked():                                               # the own room doubles, not the logical capacity (the parent's part is not the fork's)
+                base = int(cache.split.max())
+                self._reallocate(cache, base + plan_capacity(cache.room, needed - base))
+            else:
+                self._reallocate(cache, plan_capacity(cache.capacity, needed))
 
     def _grown(self, cache, lengths, K):
         if cache.lengths is None:
@@ -929,10 +1001,125 @@ class MIGT:
         rep.kv = [kv.view(cache.B, -1).repeat_interleave(S, 0).view(-1, kv.shape[1]) for kv in cache.kv]
         rep.B = cache.B * S
         rep.lengths = None if cache.lengths is None else np.repeat(cache.lengths, S).astype(np.int32)
+        if cache.forked():                                                   # the own buffers are copied, the parent's still shared: (b S + s) // (share S) = b // share
+            rep.split = np.repeat(cache.split, S).astype(np.int32)
+            rep.share = cache.share * S
+            rep._split_dev = torch.from_numpy(rep.split).to(self.device)
+            rep._parent = None
         return rep
 
+    # ------------------------------------------------------------------ forks: children that share a cache's views and own what they add
+    def _fork(self, cache, S, room):
+        from .render import plan_fork
+        if cache.forked():
+            raise ValueError('fork: a fork of a fork is not supported: fork cache.materialize() instead')
+        L = int(np.prod(cache.tshape))
+        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
+        cache.check(self)
+        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) or cache.B * int(S) > 65535:
+            raise ValueError(f'fork: S, an integer >= 1 with B * S <= 65535, expected, got {S}')
+        room = 0 if room is None else room
+        if isinstance(room, bool) or not isinstance(room, (int, np.integer)) or int(room) < 0:
+            raise ValueError(f'fork: room, an integer >= 0, expected, got {room}')
+        S, room = int(S), int(room)
+        split, _ = plan_fork(cache.filled(), S)
+        d = self.config.d_model
+        child = cache.alias()
+        child.parent_kv = list(cache.kv)
+        child.parent_capacity = cache.capacity
+        child.kv = [torch.empty((cache.B * S * room * L, 3 * d), dtype=kv.dtype, device=self.device) for kv in cache.kv]
+        child.B = cache.B * S
+        child.split, child.share, child.room = split, S, room
+        child.lengths = split.copy()
+        child.C = int(split.max()) if split.size else 0
+        child.capacity = child.C + room
+        child._split_dev = torch.from_numpy(split).to(self.device)
+        import weakref
+        child._parent = weakref.ref(cache)
+        return child
+
+    def _materialize(self, cache):
+        cache.check(self)
+        d, L, dev = self.config.d_model, int(np.prod(cache.tshape)), self.device
+        B = cache.B
+        out = cache.alias()
+        if not cache.forked():
+            out.kv = [kv.clone() for kv in cache.kv]
+            return out
+        S, Bp, Cp, room = cache.share, cache.B // cache.share, cache.parent_capacity, cache.room
+        cap = cache.capacity                                                 # split.max() + room: every logical view has its place
+        pos0 = torch.zeros(Bp, dtype=torch.int32, device=dev)
+        kvs = []
+        for pkv, own in zip(cache.parent_kv, cache.kv):
+            dst = torch.empty((B * cap * L, 3 * d), dtype=own.dtype, device=dev)
+            for s in range(S):                                               # the parent's views to child s of every scene (views beyond cap are skipped)
+                ops.kv_append(pkv, dst[s * cap * L:], Bp, Cp, L, d, 3 * d, 3 * d, S * cap * L * 3 * d, cap, pos0)
+            if room:                                                         # the own views behind each scene's split, over whatever the parent held there
+                ops.kv_append(own, dst, B, room, L, d, 3 * d, 3 * d, cap * L * 3 * d, cap, cache._split_dev)
+            kvs.append(dst)
+        out.kv = kvs
+        out.parent_kv = out.parent_capacity = out.split = out.share = out.room = out._parent = out._split_dev = None
+        return out
+
+    def adopt_from_fork(self, parent, child, which, score=None):
+        """Keep one child's trajectory: the own views of child ``which[b]`` of every scene b are appended to ``parent`` — one
+        ``ops.kv_append`` per layer on a gathered source, no row is run again — which then holds what ``append_to_context`` of those views
+        would have left (the child computed them against the parent's views and its own earlier ones: the same launches).  ``which``: int
+        [B] (host or device) in [0, S), or ``'best'`` with ``score`` [B,S] (or [B,S,T], summed over T in order): the child with the
+        largest score, ties going to the lowest index (``render.choose_best``).  Refused: a child of another cache, and a parent whose
+        lengths have moved since the fork.  ``parent`` grows in place by the children's number of own views.  -> the adopted child per
+        scene, int64 [B] (host)."""
+        from .render import choose_best, plan_fork_lengths
+        if not isinstance(parent, ContextCache) or not isinstance(child, ContextCache):
+            raise TypeError('adopt_from_fork: two ContextCaches expected')
+        if not child.forked() or parent.forked():
+            raise ValueError('adopt_from_fork: a plain parent cache and a cache forked from it expected')
+        if child._parent is None or child._parent() is not parent:
+            raise ValueError('adopt_from_fork: the child was not forked from this parent')
+        parent.check(self)
+        child.check(self)
+        S, B = child.share, parent.B
+        lengths = parent.filled()
+        if child.B != B * S or not np.array_equal(np.repeat(lengths, S), child.split):
+            raise ValueError(f'adopt_from_fork: the parent has grown since the fork (lengths {lengths.tolist()}, forked at '
+                             f'{child.split[::S].tolist()}): fork again')
+        if isinstance(which, str):
+            if which != 'best' or score is None:
+                raise ValueError("adopt_from_fork: which = 'best' goes with score [B,S]")
+            sc = score.detach().float().cpu().numpy() if isinstance(score, torch.Tensor) else np.asarray(score, dtype=np.float32)
+            if sc.ndim == 3:
+                tot = np.zeros(sc.shape[:2], dtype=np.float32)
+                for t in range(sc.shape[2]):                                 # in order, in fp32
+                    tot = tot + sc[:, :, t]
+                sc = tot
+            if sc.shape != (B, S):
+                raise ValueError(f'adopt_from_fork: score [B={B},S={S}] expected, got {sc.shape}')
+            which = choose_best(sc)
+        else:
+            if score is not None:
+                raise ValueError("adopt_from_fork: score goes with which = 'best'")
+            which = np.asarray(which.detach().cpu().numpy() if isinstance(which, torch.Tensor) else which)
+            if which.shape != (B,) or which.dtype == np.bool_ or not np.issubdtype(which.dtype, np.integer) or (
+                    which.size and (which.min() < 0 or which.max() >= S)):
+                raise ValueError(f'adopt_from_fork: which, integers [B={B}] in [0, S={S}), expected, got {which}')
+        own = plan_fork_lengths(child.split, child.filled(), child.room)
+        K = int(own[0]) if own.size else 0
+        which = which.astype(np.int64)
+        if K == 0:
+            return which
+        d, L, dev = self.config.d_model, int(np.prod(parent.tshape)), self.device
+        self._reserve(parent, int(lengths.max()) + K)
+        cap = parent.capacity
+        pos = torch.from_numpy(lengths).to(dev)
+        idx = torch.from_numpy(np.arange(B, dtype=np.int64) * S + which).to(dev)
+        for i, own_kv in enumerate(child.kv):
+            src = own_kv.view(B * S, child.room * L, 3 * d)[idx, :K * L].reshape(B * K * L, 3 * d)
+            ops.kv_append(src, parent.kv[i], B, K, L, d, 3 * d, 3 * d, cap * L * 3 * d, cap, pos)
+        self._grown(parent, lengths, K)
+        return which
+
     def rollout_from_context(self, cache, path_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 1, top_p: float = 1.0,
-                             seed: int = 0, return_logits: bool = False, fused_step: bool = True):
+                             seed: int = 0, return_logits: bool = False, fused_step: bool = True, fork: bool = False):
         """A camera path whose frames agree with each other: ``path_cameras`` fp32 [B,T,7] in the context's (relative, normalised) frame.
         For t = 0 ... T-1 view t is generated from the cache as it stands — the photographs AND the views 0 ... t-1 — and the generated
         code map is appended with camera t: by definition the loop ``sample_from_context`` of 1 view (``view0 = t``), then
@@ -948,7 +1135,10 @@ class MIGT:
         definition.  Both give the definition's bits where the dense layers take one kernel for both row counts.
         ``top_k = 1`` (default) is the arg-max roll-out whatever the seed.  ``n_samples`` = S > 1: S independent trajectories per scene on
         a cache replicated to B*S scenes (scene b's copies at b*S ... b*S+S-1); the noise of token l of step t of trajectory (b, s) is
-        keyed as ``sample_from_context`` keys scene b*S+s, view t, sample 0 — reproducible, and a prefix of a longer roll-out."""
+        keyed as ``sample_from_context`` keys scene b*S+s, view t, sample 0 — reproducible, and a prefix of a longer roll-out.
+        ``fork=True`` (with S > 1; opt-in): the S trajectories run on ``cache.fork(S, room=T)`` instead of a replicated cache — the
+        photographs' keys are read where they lie, only the T generated views per trajectory get buffers — with the same bits, the same
+        noise keys and the fork as the returned ``cache`` (``adopt_from_fork`` keeps one trajectory in ``cache``)."""
         path_cameras, L = self._check_growing(cache, path_cameras, 'rollout_from_context', 'path_cameras')
         c, dev = self.config, self.device
         d, nE, tshape = c.d_model, c.n_embeddings, cache.tshape
@@ -960,8 +1150,10 @@ class MIGT:
         if T * L >= 1 << 32 or B * S >= 1 << 31:
             raise ValueError(f'rollout_from_context: T * {L} < 2^32 and B * n_samples < 2^31 expected, got T = {T}, B = {B}, n_samples = {S}')
         from .render import plan_rollout_lengths, plan_replication, rollout_row_ids
+        if fork and S > 1 and cache.forked():
+            raise ValueError('rollout_from_context: fork=True on a forked cache would be a fork of a fork: pass cache.materialize()')
         if S > 1:
-            cache = self._replicate(cache, S)
+            cache = self._fork(cache, S, T) if fork else self._replicate(cache, S)
             path_cameras = path_cameras[torch.from_numpy(plan_replication(B, S)).to(dev)]
         Bs = B * S
         M = Bs * L

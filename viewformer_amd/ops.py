@@ -624,6 +624,41 @@ def attn_prefix(q, k, v, kp, vp, out, B, H, C, N, L, ldq, ldk, ldv, ldkp, ldvp, 
     return out
 
 
+def attn_prefix_fork(q, k, v, kp, vp, kp2, vp2, out, B, H, C, C2, N, L, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldkp2, ldvp2,
+                     prefix_stride2, ldo, ctx_len, split, share, bf16=False, dh=64):
+    """``attn_prefix(ctx_len=...)`` over a forked cache (vf_attn_prefix_fork_*): ``B`` CHILD scenes; child scene b reads the first
+    ``split[b]`` views of parent scene ``b // share`` from kp / vp (``C`` views of room per parent scene, scenes ``prefix_stride``
+    elements apart) and then its own views from kp2 / vp2 (``C2`` views of room per child scene, scenes ``prefix_stride2`` apart; with
+    ``C2 = 0`` they may be None).  ``ctx_len`` int32 device [B*N] counts logical views, ``split`` int32 device [B].  A view gets the bits
+    of ``attn_prefix(ctx_len=...)`` on the materialised cache (the parent's first split views, then the own views)."""
+    lib = _lib.load()
+    _chk(ctx_len, torch.int32, 'ctx_len')
+    _chk(split, torch.int32, 'split')
+    if ctx_len.numel() != B * N or not ctx_len.is_contiguous():
+        raise ValueError(f'attn_prefix_fork: ctx_len int32 [B*N = {B * N}] contiguous expected, got {tuple(ctx_len.shape)}')
+    if split.numel() != B or not split.is_contiguous():
+        raise ValueError(f'attn_prefix_fork: split int32 [B = {B}] contiguous expected, got {tuple(split.shape)}')
+    if (kp2 is None) != (vp2 is None) or (kp2 is None and C2 > 0):
+        raise ValueError('attn_prefix_fork: kp2 and vp2 expected (None for both only with C2 = 0)')
+    own = () if kp2 is None else (kp2, vp2)
+    if bf16:
+        o16 = out.dtype == torch.bfloat16
+        i16 = q.dtype == torch.bfloat16
+        for t in (q, k, v, kp, vp) + own:
+            _chk(t, torch.bfloat16 if i16 else torch.float32, 'q/k/v/prefix')
+        check(lib.vf_attn_prefix_fork_bf16(_p(q), _p(k), _p(v), _p(kp), _p(vp), 1 if i16 else 0, _p(out if o16 else _f32(out)),
+                                           1 if o16 else 0, B, H, C, N, L, dh, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, ldo, _p(ctx_len),
+                                           _p(kp2), _p(vp2), C2, ldkp2, ldvp2, prefix_stride2, _p(split), share, _stream()),
+              'vf_attn_prefix_fork_bf16')
+        return out
+    for t in (q, k, v, kp, vp, out) + own:
+        _f32(t, 'q/k/v/prefix/out')
+    check(lib.vf_attn_prefix_fork_f32eq(_p(q), _p(k), _p(v), _p(kp), _p(vp), _p(out), B, H, C, N, L, dh, ldq, ldk, ldv, ldkp, ldvp,
+                                        prefix_stride, ldo, _p(ctx_len), _p(kp2), _p(vp2), C2, ldkp2, ldvp2, prefix_stride2, _p(split), share,
+                                        _stream()), 'vf_attn_prefix_fork_f32eq')
+    return out
+
+
 def attn_prefix_bwd(q, k, v, kp, vp, dout, dqkv, B, H, C, N, L, ldq, ldk, ldv, ldkp, ldvp, prefix_stride, lddo, lddqkv, dh=64, ctx_len=None):
     """Backward of ``attn_prefix`` over the query views (csrc/attention_prefix_bwd.hip): q / k / v / kp / vp / ctx_len as there (bf16 or
     fp32 tensors, one dtype for all five; widened to fp32 on load, fp32 MFMA on either arm), ``dout`` fp32 [B*N*L][lddo] the gradient of

@@ -40,6 +40,11 @@ error (the same launches per row, except that a prefilled view's attention is th
 kernel); ``rollout(path)`` is the loop
 "``sample`` one view at path[t] (``top_k = 1``: ``render``), ``append`` it with path[t]".
 
+Forks: S trajectories from one context need not copy it.  ``r.fork(S)`` is a renderer of B*S what-if scenes whose cache
+(``ContextCache.fork``) reads r's views where they lie and owns only what it adds; ``r.rollout(path, n_samples=S, fork=True)`` rolls the
+trajectories out on such a fork — the bits of the replicated roll-out — and ``adopt='best'`` (or an index per scene) keeps one of them in
+r's own context without running a row again.  ``score_gradient`` and ``refine`` need ``cache.materialize()``, the plain copy.
+
 Not covered here: contexts that change per query other than by growing at the end (the 7-Scenes pose-refinement loop; sliding windows or
 eviction, which would change what the later views' keys are); they keep their evaluator.
 """
@@ -187,6 +192,52 @@ def plan_replication(B: int, S: int):
     return np.repeat(np.arange(B, dtype=np.int64), S)
 
 
+def plan_fork(lengths, S: int):
+    """The children of a fork of scenes with ``lengths`` [B] filled views, S per scene: (split int32 [B*S], parent int64 [B*S]).  Child
+    scene b*S+s (the order of ``plan_replication``) starts at ``split = lengths[b]`` logical views, all of them parent scene b's.  Pure."""
+    a = np.asarray(lengths)
+    if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or S < 1 or (a.size and a.min() < 0):
+        raise ValueError(f'plan_fork: lengths, [B] integers >= 0, and S >= 1 expected, got {lengths} and {S}')
+    parent = plan_replication(a.shape[0], S)
+    return np.ascontiguousarray(a[parent].astype(np.int32)), parent
+
+
+def map_fork_views(split, n_views: int):
+    """Where the logical views 0 ... n_views-1 of every scene of a fork lie: (segment int8 [B,n_views], view int32 [B,n_views]) —
+    segment 0 = the parent's buffers, view s, for s < split[b]; segment 1 = the scene's own buffers, view s - split[b], otherwise.  This
+    is the mapping of ``vf_attn_prefix_fork_*`` and of the own-buffer appends.  Pure."""
+    a = np.asarray(split)
+    if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or n_views < 0 or (a.size and a.min() < 0):
+        raise ValueError(f'map_fork_views: split, [B] integers >= 0, and n_views >= 0 expected, got {split} and {n_views}')
+    s = np.arange(n_views, dtype=np.int64).reshape(1, n_views)
+    sp = a.astype(np.int64).reshape(-1, 1)
+    own = s >= sp
+    return own.astype(np.int8), np.where(own, s - sp, s).astype(np.int32)
+
+
+def plan_fork_lengths(split, lengths, room: int):
+    """The own views of a fork's scenes: ``lengths - split`` int32 [B], validated — logical ``lengths`` [B] of at least ``split`` and at
+    most ``split + room``, and the same number of own views in every scene (children grow together).  Pure."""
+    sp, ln = np.asarray(split), np.asarray(lengths)
+    ok = (sp.ndim == 1 and sp.shape == ln.shape and np.issubdtype(sp.dtype, np.integer) and np.issubdtype(ln.dtype, np.integer)
+          and sp.dtype != np.bool_ and ln.dtype != np.bool_ and room >= 0)
+    if not ok or (sp.size and (sp.min() < 0 or (ln < sp).any() or (ln > sp.astype(np.int64) + room).any())):
+        raise ValueError(f'plan_fork_lengths: split <= lengths <= split + room = {room}, [B] integers, expected, got {split} and {lengths}')
+    own = (ln.astype(np.int64) - sp).astype(np.int32)
+    if own.size and (own != own[0]).any():
+        raise ValueError(f'plan_fork_lengths: every scene holds the same number of own views, got {own.tolist()}')
+    return own
+
+
+def choose_best(score):
+    """The trajectory to keep per scene: ``score`` [B,S] floats -> int64 [B], the index of the largest score, ties going to the lowest
+    index; a NaN never wins against a number (a row of NaNs gives 0).  Pure."""
+    a = np.asarray(score, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError(f'choose_best: score [B,S >= 1] expected, got {a.shape}')
+    return np.argmax(np.where(np.isnan(a), -np.inf, a), axis=1).astype(np.int64)
+
+
 def rollout_row_ids(n_scenes: int, t: int, L: int):
     """Noise keys of step t of a roll-out over ``n_scenes`` (= B*S) scenes: int64 [n_scenes*L], (scene << 32) | (t L + l) — what
     ``MIGT.sample_from_context`` gives view ``t`` of that scene (``view0 = t``), so a trajectory's draws do not depend on T.  Pure."""
@@ -301,8 +352,28 @@ class ViewRenderer:
         self._add_codes(before, codes)
         return self
 
+    def fork(self, S: int, room=None):
+        """S what-if renderers per scene: a new ViewRenderer of B*S scenes (scene b's children at b*S ... b*S+S-1) on the same model
+        objects, whose cache is ``self.cache.fork(S, room)`` — it reads this renderer's context where it lies and owns only what it
+        adds — with ``transform``, ``context_codes`` and ``n_context`` repeated per child.  Its ``append``, ``rollout(keep=True)``,
+        ``render``, ``sample``, ``score`` and ``localize`` work as on any renderer and never touch this one; ``score_gradient`` and
+        ``refine`` need ``cache.materialize()``."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.fork: set_context() first')
+        if isinstance(S, bool) or int(S) != S or int(S) < 1:
+            raise ValueError(f'fork: S, an integer >= 1, expected, got {S}')
+        S = int(S)
+        r = ViewRenderer(self.transformer, self.codebook)
+        r.fused_score, r.fused_tail = self.fused_score, self.fused_tail
+        work = self._own_lengths(self.cache.alias())                         # (the ragged batch's valid views: the children start behind them)
+        r.cache = work.fork(S, room)
+        r.transform = None if self.transform is None else self.transform.repeat_interleave(S, 0)
+        r.context_codes = self.context_codes.repeat_interleave(S, 0)
+        r.n_context = None if self.n_context is None else np.repeat(self.n_context, S).astype(np.int32)
+        return r
+
     def rollout(self, path_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 1, top_p: float = 1.0, seed: int = 0,
-                return_codes: bool = False, keep: bool = True, fused_step: bool = None):
+                return_codes: bool = False, keep: bool = True, fused_step: bool = None, fork: bool = False, adopt=None):
         """A fly-through whose frames agree with each other: ``path_cameras`` [B,T,7] in the caller's world frame.  Frame t is generated
         from the photographs AND the frames 0 ... t-1 (``MIGT.rollout_from_context``: the model's autoregressive answer), where
         ``render(path)`` draws every frame from the photographs alone -> dict(generated_images uint8 [B,T,H,W,3], log_likelihood fp32
@@ -312,9 +383,18 @@ class ViewRenderer:
         afterwards in chunks of MAX_SCENES_PER_CALL.  ``keep`` (default, S = 1): the generated frames stay in the context, as ``append``
         would leave them; ``keep=False`` rolls out on a copy of the lengths and leaves the renderer's context as it was (the appended
         rows are beyond its lengths again).  With S > 1 the roll-out runs on a replicated cache and the renderer's own is never
-        replaced.  ``fused_step``: None = the model's default step, True / False = the one-pass / two-pass step, for A/B runs."""
+        replaced.  ``fused_step``: None = the model's default step, True / False = the one-pass / two-pass step, for A/B runs.
+        ``fork=True`` (S > 1; opt-in): the trajectories run on a fork of the context (``MIGT.rollout_from_context(fork=True)``: the
+        photographs' keys are shared, not replicated; same bits).  ``adopt`` (with ``fork=True`` and S > 1): ``'best'`` or an int [B] —
+        after the roll-out ONE trajectory per scene stays in the renderer's own context (``MIGT.adopt_from_fork``; no row is run
+        again), ``'best'`` being the one with the largest sum of ``log_likelihood`` over T, ties going to the lowest index;
+        ``context_codes`` and ``n_context`` follow as with ``keep=True`` for S = 1, and the result gains ``adopted`` int64 [B]."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.rollout: set_context() first')
+        if adopt is not None and not (fork and int(n_samples) > 1):
+            raise ValueError('rollout: adopt goes with fork=True and n_samples > 1 (keep=True keeps the one trajectory of n_samples = 1)')
+        if adopt is not None and isinstance(adopt, str) and adopt != 'best':
+            raise ValueError(f"rollout: adopt 'best' or an int [B] expected, got {adopt!r}")
         tm, cm = self.transformer, self.codebook
         dev = cm.device
         B = self.cache.B
@@ -327,17 +407,30 @@ class ViewRenderer:
         T = path_cameras.shape[1]
         t = tm.config.token_image_size
         grow = keep and S == 1
-        work = self._own_lengths(self.cache if grow else self.cache.alias())
+        work = self._own_lengths(self.cache if grow or adopt is not None else self.cache.alias())
         before = work.filled()
         kw = {} if fused_step is None else dict(fused_step=bool(fused_step))
+        if fork:
+            kw['fork'] = True
         out = tm.rollout_from_context(work, query_poses(path_cameras, self.transform), n_samples=S,
                                       temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, return_logits=return_codes, **kw)
         codes = out['codes']                                             # [B,S,T,t,t]
         if grow and T:
             self._add_codes(before, codes[:, 0].to(torch.int32))
+        which = None
+        if adopt is not None:
+            if isinstance(adopt, str):
+                which = tm.adopt_from_fork(self.cache, out['cache'], 'best', score=out['log_likelihood'])
+            else:
+                which = tm.adopt_from_fork(self.cache, out['cache'], adopt)
+            if T:
+                pick = torch.from_numpy(which).to(codes.device)
+                self._add_codes(before, codes[torch.arange(B, device=codes.device), pick].to(torch.int32))
         img, _ = self._decode(codes.reshape(B * S * T, t, t))
         lead = (B, T) if S == 1 else (B, S, T)
         res = dict(generated_images=img.view(*lead, *img.shape[1:]), log_likelihood=out['log_likelihood'].view(*lead))
+        if which is not None:
+            res['adopted'] = torch.from_numpy(which)
         if return_codes:
             res.update(generated_codes=codes.view(*lead, t, t), token_log_prob=out['token_log_prob'].view(*lead, t, t),
                        logits=out['logits'].view(*lead, t, t, out['logits'].shape[-1]))
@@ -542,6 +635,8 @@ class ViewRenderer:
         chunking."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.score_gradient: set_context() first')
+        if self.cache.forked():
+            raise ValueError('ViewRenderer.score_gradient: the backward pass has no fork arm: set the cache to cache.materialize() first')
         query_cameras = self._world_cameras('score_gradient', query_cameras)
         B, N = self.cache.B, query_cameras.shape[1]
         codes = self._photo_codes('score_gradient', images, codes, N)
@@ -567,6 +662,8 @@ class ViewRenderer:
         ``return_trace`` trace fp32 [steps+1,B,N]).  N is walked in chunks of whole views; views are refined independently of each other."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.refine: set_context() first')
+        if self.cache.forked():
+            raise ValueError('ViewRenderer.refine: the backward pass has no fork arm: set the cache to cache.materialize() first')
         B = self.cache.B
         if cameras0 is not None:
             cameras0 = self._world_cameras('refine', cameras0)
