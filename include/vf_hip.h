@@ -367,6 +367,37 @@ int vf_attn_prefix_bwd_f32(const void* q, const void* k, const void* v, const vo
  * B, K, L, d or capacity == 0: no-op, VF_OK. */
 int vf_kv_append(const void* qkv, void* cache, int elem_bytes, int B, int K, int L, int d, int ld_src, int ld_dst, int64_t cache_stride,
                  int capacity, const int32_t* pos, void* stream);
+/* Pack the K and V thirds of a context cache to OCP e4m3 bytes with one power-of-two fp32 scale per (scene, view, head) tile of
+ * 64 tokens x 64 features (csrc/kv_pack.hip; ContextCache.pack('e4m3')).  cache: a layer's buffer as vf_kv_append takes it — rows
+ * [C*L][ld_src] per scene, thirds (V, Q, K) of d = 64 H columns each, scenes cache_stride elements apart, elem_bytes 2 (bf16) or 4 (fp32).
+ * lengths: DEVICE pointer to [B] int32; view c of scene b is packed iff c < min(lengths[b], C) — of any other view nothing is read and
+ * nothing written.  Scale of a tile: 2^e, e the smallest integer with absmax <= 448 * 2^e, taken from the exponent and mantissa fields of
+ * absmax (e = ea - 8 if the 23-bit mantissa field <= 0x600000, else ea - 7), e = 0 when absmax is 0 or not finite, clamped to [-100, 100];
+ * NaN elements do not enter absmax.  Elements: x * 2^-e, saturated to +-448, rounded to nearest even; a NaN stays NaN.  Output, tile-major:
+ *   kq: tile (b, c, h) = 4096 bytes [64 keys][64 features] at byte b * q_scene_stride + c * q_view_stride + h * 4096;
+ *   vq: the same place in its own buffer, [64 features][64 keys] (V transposed);
+ *   kscale / vscale: fp32 at element b * s_scene_stride + c * s_view_stride + h.
+ * value = e4m3 * scale is exactly a bf16 number and never a subnormal one.  Footprint: reads the K and V thirds of the packed views and
+ * lengths; writes exactly their tiles and scales.  NULL pointers, cache / kq / vq not 16-byte aligned, elem_bytes not in {2, 4}, a negative
+ * size, H <= 0, ld_src < 3 * 64 H, ld_src / cache_stride times elem_bytes not a multiple of 16, q_view_stride < 4096 H, q_*_stride % 16,
+ * s_view_stride < H, a negative scene stride, or (B > 1) a scene stride below one scene's extent: VF_ERR_BAD_ARG; L != 64, B C > 2^31 - 1,
+ * H > 65535: VF_ERR_UNSUPPORTED; all before any launch.  B = 0 or C = 0: no-op, VF_OK. */
+int vf_kv_pack_e4m3(const void* cache, int elem_bytes, void* kq, void* vq, float* kscale, float* vscale, int B, int C, int H, int L,
+                    int ld_src, int64_t cache_stride, int64_t q_view_stride, int64_t q_scene_stride, int64_t s_view_stride,
+                    int64_t s_scene_stride, const int32_t* lengths, void* stream);
+/* vf_attn_prefix_var_bf16 over a cache packed by vf_kv_pack_e4m3 (the kernel's Q8 instantiation): kq / vq / kscale / vscale and the four
+ * strides as there, C = the views of room per scene in the packed buffers; q / k / v (bf16 or fp32 by in_bf16), out, ld*, ctx_len (a length
+ * per query view, clamped to [0, C]) as the VAR entry's.  A packed tile is fetched as one contiguous 4 KiB block, dequantised (e4m3 * scale,
+ * exact in bf16) while it is staged into LDS, and consumed by the bf16 arm's arithmetic unchanged.  Contract:
+ *   - a view gets, bit for bit, what vf_attn_prefix_var_bf16 gives it on the dequantised cache;
+ *   - the kernel writes exactly the logical output elements;
+ *   - a view's result does not depend on packed bytes or scales of views at or beyond its length.
+ * Checks as the VAR entry's, and NULL kq / vq / kscale / vscale, kq / vq not 16-byte aligned, q_view_stride < 4096 H, q_*_stride % 16,
+ * s_view_stride < H or a negative scene stride: VF_ERR_BAD_ARG; all before any launch.  B = 0 or N = 0: no-op, VF_OK. */
+int vf_attn_prefix_q8_bf16(const void* q, const void* k, const void* v, const void* kq, const void* vq, const float* kscale, const float* vscale,
+                           int in_bf16, void* out, int out_bf16, int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv,
+                           int64_t q_view_stride, int64_t q_scene_stride, int64_t s_view_stride, int64_t s_scene_stride, int ldo,
+                           const int32_t* ctx_len, void* stream);
 /* Single-head spatial self-attention of the VQGAN AttnBlock, fused (csrc/attn_spatial.hip): replaces the core of AttnBlock.forward
  * (vqgan_th.py:124-141) — scores = q^T k * scale, softmax over the keys, h = v . p^T — per image of HW tokens x C channels, from the
  * fused q|k|v projection qkv [n_img * HW][ld] (q at column 0, k at C, v at 2C); out [n_img * HW][ldo].  Exact fp32

@@ -33,6 +33,15 @@
 // in the workgroup.  Staging, the group logic, the key order (parent ascending, own ascending, the view's own tile) and the arithmetic are
 // those of VAR: a view gets the bits that VAR gives it on the materialised cache (parent views [0, split) and the own views, contiguous).
 // The fixed-C and VAR instantiations take prefix_args as before and compile to what they were.
+//
+// Packed caches (vf_attn_prefix_q8_bf16, the bf16 kernel's Q8 instantiation; csrc/kv_pack.hip makes them): the prefix is e4m3 bytes in
+// 64 x 64 tiles — K [key][feature], V [feature][key], the transposed image the V^T LDS rows want — with one power-of-two fp32 scale per
+// (scene, view, head).  Only prefetch and stage differ from VAR: a prefix step fetches each tile as one contiguous 4 KiB block (16 bytes per
+// thread) and its scale by a load that is uniform in the workgroup; stage converts, multiplies by the scale and casts to bf16 — exact,
+// since an e4m3 value times a power of two is a bf16 number — and writes the LDS image the other modes build (K rows as 16-byte writes,
+// V^T rows, 136 B apart, as 8-byte writes).  The group's own tiles come from q / k / v as before.  The consumer half of the loop, the key
+// order, gmax / mylen, the softmax and the stores are shared: a view gets, bit for bit, what VAR gives it on the dequantised cache.  A
+// length is clamped to [0, C], so no value of ctx_len takes a load outside the packed buffers.  FIXED, VAR and FORK compile to what they were.
 #include "vf_common.h"
 #include "../../include/vf_hip.h"
 
@@ -67,9 +76,17 @@ struct fork_args : prefix_args {
     const int* split;                                 // [B]: logical view s of scene b is parent view s if s < split[b], else own view s - split[b]
 };
 
-enum { FIXED = 0, VAR = 1, FORK = 2 };
+// Q8 (bf16 arm only): the prefix is a PACKED cache (csrc/kv_pack.hip) — e4m3 tiles with one power-of-two scale each; kp / vp are not read
+struct q8_args : prefix_args {
+    const unsigned char* kq; const unsigned char* vq;  // tile (b, s, h) at b * qscene + s * qview + h * 4096 bytes: K [key][feature], V [feature][key]
+    const float* kscale; const float* vscale;          // its scales at b * sscene + s * sview + h
+    long long qview, qscene, sview, sscene;
+};
+
+enum { FIXED = 0, VAR = 1, FORK = 2, Q8 = 3 };
 template <int MODE> struct args_of { typedef prefix_args type; };
 template <> struct args_of<FORK> { typedef fork_args type; };
+template <> struct args_of<Q8> { typedef q8_args type; };
 
 // VAR / FORK: the length of query view (b, n), clamped to the room (VAR: the cache's capacity; FORK: the scene's split + the own room); fixed-C: C
 template <int MODE>
@@ -142,7 +159,20 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const typename
     }
     const int nsteps = gmax + nown;                              // gmax prefix tiles, then the group's own tiles
     f32x4 kreg[4], vreg[4];
+    uint4 kq8, vq8;                                              // Q8: this thread's 16 bytes of the packed K tile and of the packed V^T tile
+    float ksc = 0.f, vsc = 0.f;                                  //     and the tile's two scales (uniform in the workgroup)
     auto prefetch = [&](int s) {
+        if constexpr (MODE == Q8) {
+            if (s < gmax) {                                          // a prefix tile: one contiguous 4 KiB block each for K and V^T
+                const size_t t0 = b * (size_t)a.qscene + (size_t)s * (size_t)a.qview + (size_t)h * (LV * DH) + (size_t)tid * 16;
+                kq8 = *reinterpret_cast<const uint4*>(a.kq + t0);
+                vq8 = *reinterpret_cast<const uint4*>(a.vq + t0);
+                const size_t s0 = b * (size_t)a.sscene + (size_t)s * (size_t)a.sview + (size_t)h;
+                ksc = a.kscale[s0];
+                vsc = a.vscale[s0];
+                return;
+            }
+        }
         const void *kb, *vb;
         size_t k0, v0_;
         int ldk_, ldv_;
@@ -172,7 +202,34 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const typename
             vreg[i] = load4(vb, v0_ + (size_t)vkey * ldv_ + s_col4 * 4, in16);
         }
     };
-    auto stage = [&]() {
+    auto stage = [&](int s) {
+        if constexpr (MODE == Q8) {
+            if (s < gmax) {                                          // e4m3 * 2^e is a bf16 value: the LDS image is the one VAR builds from the unpacked cache
+                const int r = tid >> 2, c16 = tid & 3;               // K: key r, features 16 c16 ...; V^T: feature r, keys 16 c16 ...
+                bf16x8 k8[2];
+                bf16x4 v4[4];
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned kw = w == 0 ? kq8.x : w == 1 ? kq8.y : w == 2 ? kq8.z : kq8.w;
+                    const unsigned vw = w == 0 ? vq8.x : w == 1 ? vq8.y : w == 2 ? vq8.z : vq8.w;
+                    const auto k01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)kw, false), k23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)kw, true);
+                    const auto v01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)vw, false), v23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)vw, true);
+                    k8[w >> 1][4 * (w & 1) + 0] = (__bf16)(k01[0] * ksc);
+                    k8[w >> 1][4 * (w & 1) + 1] = (__bf16)(k01[1] * ksc);
+                    k8[w >> 1][4 * (w & 1) + 2] = (__bf16)(k23[0] * ksc);
+                    k8[w >> 1][4 * (w & 1) + 3] = (__bf16)(k23[1] * ksc);
+                    v4[w][0] = (__bf16)(v01[0] * vsc);
+                    v4[w][1] = (__bf16)(v01[1] * vsc);
+                    v4[w][2] = (__bf16)(v23[0] * vsc);
+                    v4[w][3] = (__bf16)(v23[1] * vsc);
+                }
+                *reinterpret_cast<bf16x8*>(Ks + r * K_LDB + c16 * 32) = k8[0];
+                *reinterpret_cast<bf16x8*>(Ks + r * K_LDB + c16 * 32 + 16) = k8[1];
+#pragma unroll
+                for (int w = 0; w < 4; ++w) *reinterpret_cast<bf16x4*>(Vt + r * VT_LDB + c16 * 32 + 8 * w) = v4[w];   // rows of 136 B: 8-byte aligned
+                return;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             bf16x4 kk;
@@ -207,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefix_bf16_kernel(const typename
     prefetch(0);
     for (int s = 0; s < nsteps; ++s) {
         __syncthreads();                                             // previous tile fully consumed
-        stage();
+        stage(s);
         __syncthreads();
         if (s + 1 < nsteps) prefetch(s + 1);
         if (!active || (s >= gmax ? s - gmax != wave : s >= mylen)) continue;      // an own tile belongs to one wave; a prefix tile to the views that reach it
@@ -570,12 +627,24 @@ int fork_check(const fork_args& a, int H) {
     return VF_OK;
 }
 
+// the packed prefix (host only)
+int q8_check(const q8_args& a, int B, int H) {
+    if (!a.kq || !a.vq || !a.kscale || !a.vscale) return VF_ERR_BAD_ARG;
+    if (((uintptr_t)a.kq | (uintptr_t)a.vq) & 15 || ((uintptr_t)a.kscale | (uintptr_t)a.vscale) & 3) return VF_ERR_BAD_ARG;
+    if (a.qview < (long long)H * LV * DH || a.qscene < 0 || (a.qview | a.qscene) & 15) return VF_ERR_BAD_ARG;   // tiles are fetched as 16-byte vectors
+    if (a.sview < H || a.sscene < 0) return VF_ERR_BAD_ARG;
+    return VF_OK;
+}
+
 template <int MODE>
 int launch_bf16(const typename args_of<MODE>::type& a, int B, int H, int L, int dh, void* stream) {
     if (MODE != FIXED && !a.ctx_len) return VF_ERR_BAD_ARG;
     int rc = prefix_check(a, B, H, L, dh);
     if constexpr (MODE == FORK) {
         if (rc == VF_OK) rc = fork_check(a, H);
+    }
+    if constexpr (MODE == Q8) {
+        if (rc == VF_OK) rc = q8_check(a, B, H);
     }
     if (rc != VF_OK) return rc;
     if (B == 0 || a.N == 0) return VF_OK;
@@ -639,6 +708,18 @@ int vf_attn_prefix_fork_bf16(const void* q, const void* k, const void* v, const 
     const fork_args a{{q, k, v, kp, vp, out, C, N, ldq, ldk, ldv, ldkp, ldvp, ldo, (long long)prefix_stride, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0,
                        ctx_len}, kp2, vp2, C2, share, ldkp2, ldvp2, (long long)prefix_stride2, split};
     return launch_bf16<FORK>(a, B, H, L, dh, stream);
+}
+
+int vf_attn_prefix_q8_bf16(const void* q, const void* k, const void* v, const void* kq, const void* vq, const float* kscale, const float* vscale,
+                           int in_bf16, void* out, int out_bf16, int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv,
+                           int64_t q_view_stride, int64_t q_scene_stride, int64_t s_view_stride, int64_t s_scene_stride, int ldo,
+                           const int32_t* ctx_len, void* stream) {
+    // kp / vp of the shared checks: the packed tiles stand in (never read through them), with the tightest leading dimension
+    const int ldt = H > 0 && H <= 65535 ? H * DH : 0;
+    const q8_args a{{q, k, v, kq, vq, out, C, N, ldq, ldk, ldv, ldt, ldt, ldo, 0LL, in_bf16 ? 1 : 0, out_bf16 ? 1 : 0,
+                     ctx_len}, (const unsigned char*)kq, (const unsigned char*)vq, kscale, vscale, (long long)q_view_stride,
+                    (long long)q_scene_stride, (long long)s_view_stride, (long long)s_scene_stride};
+    return launch_bf16<Q8>(a, B, H, L, dh, stream);
 }
 
 int vf_attn_prefix_fork_f32eq(const float* q, const float* k, const float* v, const float* kp, const float* vp, float* out,

@@ -42,14 +42,21 @@ class ContextCache:
     filled length per child scene at fork time, ``share`` = S (child scene b reads parent scene b // S), ``room`` = own views of room
     per child scene, and ``kv[i]`` the OWN buffers [B*S*room*L, 3*d_model].  ``filled()``, ``lengths``, ``C`` and ``capacity`` count
     LOGICAL views: logical view s of scene b is parent view s below ``split[b]``, own view ``s - split[b]`` otherwise
-    (``render.map_fork_views``).  Every child holds the same number of own views."""
+    (``render.map_fork_views``).  Every child holds the same number of own views.
+
+    A PACKED cache (``pack()``) is read-only and holds no Q third: ``packed`` is ``'kv'`` — ``kv[i]`` = (K, V), two
+    contiguous [B*C*L, d_model] tensors in the cache's dtype, served by the plain prefix attention with the bits of the source cache —
+    or ``'e4m3'`` (bf16 arm) — ``kv[i]`` = (kq uint8 [B*C, H, 64 keys, 64 features], vq uint8 [B*C, H, 64 features, 64 keys], kscale,
+    vscale fp32 [B*C, H]): OCP e4m3 bytes with one power-of-two scale per (scene, view, head), served by ``ops.attn_prefix_q8`` with the
+    bits of the bf16 arm on the dequantised cache (``unpack()``).  Both are tight (``capacity`` = ``C``, the longest scene)."""
     _FIELDS = ('kv', 'B', 'C', 'tshape', 'device', 'arm', 'act16', 'qkv16', '_owner', '_weights', 'capacity', 'lengths',
-               'parent_kv', 'parent_capacity', 'split', 'share', 'room', '_parent', '_split_dev')
+               'parent_kv', 'parent_capacity', 'split', 'share', 'room', '_parent', '_split_dev', 'packed')
     __slots__ = _FIELDS + ('__weakref__',)
 
     def __init__(self, model, kv, B, C, tshape, capacity=None, lengths=None):
         import weakref
         self.parent_kv = self.parent_capacity = self.split = self.share = self.room = self._parent = self._split_dev = None
+        self.packed = None
         self.kv, self.B, self.C, self.tshape = kv, B, C, tuple(tshape)
         self.capacity = C if capacity is None else int(capacity)
         self.lengths = None if lengths is None else np.array(lengths, dtype=np.int32).reshape(B)
@@ -104,6 +111,31 @@ class ContextCache:
         """A plain ContextCache of this fork's B*S scenes in buffers of its own: the parent's views at position 0, the own views behind
         them, copied bit for bit by ``ops.kv_append`` (every result on it has the fork's bits).  On a plain cache: a copy."""
         return self._model('materialize')._materialize(self)
+
+    def pack(self, dtype=None):
+        """A packed, READ-ONLY ContextCache of the same scenes in buffers of its own (this cache is left untouched), tight (capacity =
+        the longest scene), lengths kept.  ``dtype=None``: the K and V thirds only, in the cache's dtype — 2/3 of the bytes, both arms,
+        every result ``torch.equal`` to this cache's.  ``dtype='e4m3'`` (``precision='bf16'`` models only): OCP e4m3 bytes with one
+        power-of-two scale per (scene, view, head) for K and one for V (``ops.kv_pack_e4m3``) — about 1/3 of the bf16 bytes; every
+        result has the bits of the bf16 arm on ``unpack()``'s dequantised cache, and what is lost is the quantisation alone.
+        ``generate`` / ``sample`` / ``score`` / ``localize_from_context`` take a packed cache as any cache; whatever grows a cache, forks
+        it or differentiates through it refuses it: ``unpack()`` first.  A fork or a packed cache is refused: ``materialize()`` /
+        ``unpack()`` first."""
+        return self._model('pack')._pack(self, dtype)
+
+    def unpack(self):
+        """A plain ContextCache (thirds V, Q, K) of a packed one, in buffers of its own: the K and V thirds bit for bit (K/V-only form)
+        or dequantised (e4m3 form: e4m3 * scale, exact in bf16), the Q third zeros — the way back to ``append_to_context``,
+        ``rollout_from_context``, ``fork`` and the gradients.  On a cache that is not packed: refused."""
+        return self._model('unpack')._unpack(self)
+
+    def nbytes(self):
+        """the bytes of this cache's own tensors, from their shapes (a fork: its own buffers, not the parent's)"""
+        n = 0
+        for t in self.kv:
+            for x in (t if isinstance(t, (tuple, list)) else (t,)):
+                n += x.numel() * x.element_size()
+        return n
 
     def check(self, model):
         if self._owner() is not model or self._weights != model._weights_version:
@@ -436,6 +468,73 @@ class MIGT:
             cache.kv[i] = dst
         cache.capacity = capacity
 
+    # ------------------------------------------------------------------ packed, read-only caches
+    @staticmethod
+    def _refuse_packed(cache, what):
+        if cache.packed is not None:
+            raise ValueError(f'{what}: a packed cache is read-only (it holds no Q third and has no room): pass cache.unpack() instead')
+
+    def _pack(self, cache, dtype):
+        if cache.forked():
+            raise ValueError('pack: a forked cache reads two segments: pack cache.materialize() instead')
+        if cache.packed is not None:
+            raise ValueError(f'pack: this cache is packed already ({cache.packed!r}): pack cache.unpack() instead')
+        if dtype is not None and dtype != 'e4m3':
+            raise ValueError(f"pack: dtype None (the K and V thirds as they are) or 'e4m3' expected, got {dtype!r}")
+        if dtype == 'e4m3' and self.precision != 'bf16':
+            raise ValueError(f"pack: dtype='e4m3' is for precision='bf16' models; the {self.precision!r} arm exists for exactness: "
+                             'pack(dtype=None) keeps its bits')
+        L = int(np.prod(cache.tshape))
+        self._check_render_shapes(L)
+        c, dev = self.config, self.device
+        d, H, B, C, cap = c.d_model, c.n_head, cache.B, cache.C, cache.capacity
+        out = cache.alias()
+        out.lengths = cache.filled() if cache.ragged() else None                 # the length route whenever the source takes it
+        out.capacity = C
+        if dtype is None:
+            out.packed = 'kv'
+            out.kv = [tuple(kv.view(B, cap * L, 3 * d)[:, :C * L, a:a + d].contiguous().view(B * C * L, d) for a in (2 * d, 0)) for kv in cache.kv]
+            return out
+        out.packed = 'e4m3'
+        lengths = torch.from_numpy(cache.filled()).to(dev)
+        kvs = []
+        for kv in cache.kv:
+            kq = torch.zeros((B * C, H, 64, 64), dtype=torch.uint8, device=dev)
+            vq = torch.zeros((B * C, H, 64, 64), dtype=torch.uint8, device=dev)
+            ks = torch.ones((B * C, H), dtype=torch.float32, device=dev)
+            vs = torch.ones((B * C, H), dtype=torch.float32, device=dev)
+            if B and C:
+                ops.kv_pack_e4m3(kv, kq, vq, ks, vs, B, C, H, L, 3 * d, cap * L * 3 * d, lengths)
+            kvs.append((kq, vq, ks, vs))
+        out.kv = kvs
+        return out
+
+    def _unpack(self, cache):
+        if cache.packed is None:
+            raise ValueError('unpack: a packed cache (ContextCache.pack) expected')
+        c, dev = self.config, self.device
+        d, H, B, C = c.d_model, c.n_head, cache.B, cache.C
+        L = int(np.prod(cache.tshape))
+        out = cache.alias()
+        out.packed = None
+        dt = torch.bfloat16 if cache.qkv16 else torch.float32
+        kvs = []
+        if cache.packed == 'e4m3':                                           # byte -> value through the 256 e4m3 numbers (exact), times the tile's scale
+            lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(dev)
+        for t in cache.kv:
+            kv = torch.zeros((B * C * L, 3 * d), dtype=dt, device=dev)
+            if cache.packed == 'kv':
+                kv[:, 2 * d:], kv[:, :d] = t[0], t[1]
+            else:
+                kq, vq, ks, vs = t
+                k = lut[kq.long()] * ks.view(B * C, H, 1, 1)                 # [B*C, H, key, feature]
+                v = lut[vq.long()] * vs.view(B * C, H, 1, 1)                 # [B*C, H, feature, key]
+                kv[:, 2 * d:] = k.permute(0, 2, 1, 3).reshape(B * C * L, d).to(dt)
+                kv[:, :d] = v.permute(0, 3, 1, 2).reshape(B * C * L, d).to(dt)
+            kvs.append(kv)
+        out.kv = kvs
+        return out
+
     def _context_lengths(self, cache, n_context, N):
         """``n_context`` of the four ``*_from_context`` methods -> int32 device tensor [B*N] for ``_query_rows``, or None (None in, on a
         cache without slack and without lengths of its own: every view sees all C cached views, the path and the launches without the
@@ -447,7 +546,7 @@ class MIGT:
         reordered here."""
         from .render import plan_context_lengths
         if n_context is None:
-            if not cache.ragged():
+            if not cache.ragged() and cache.packed != 'e4m3':                # (the e4m3 attention is a length kernel: its default lengths are all C)
                 return None
             plan = plan_context_lengths(cache.filled(), cache.B, N, cache.C)
         else:
@@ -475,7 +574,9 @@ class MIGT:
         layer's fused c_attn output in a buffer of its own, the LayerNorm-2 output), then the final h that ``ln_f`` reads.  Same launches
         on the same values: the hidden states keep their bits.  With ``tail='all'`` only.
         A forked cache (``ContextCache.fork``) takes the fork route here and nowhere else: ``ops.attn_prefix_fork`` over the parent's
-        buffers and the own ones, and ``append_at`` (logical) writes the own buffers at ``append_at - split``."""
+        buffers and the own ones, and ``append_at`` (logical) writes the own buffers at ``append_at - split``.
+        A packed cache (``ContextCache.pack``) takes its routes here and nowhere else: the K/V-only form the same ``ops.attn_prefix`` on
+        its two tight tensors (leading dimension d), the e4m3 form ``ops.attn_prefix_q8``; it is read-only (no ``append_at``, no ``save``)."""
         c, dev = self.config, self.device
         B, C = cache.B, cache.capacity                                       # the attention's C is the room: lengths say what is filled
         if save is not None and tail != 'all':
@@ -485,6 +586,11 @@ class MIGT:
         M = B * N * L
         if append_at is not None and n_context is None:
             raise ValueError('_query_rows: appended views carry their context lengths')
+        packed = cache.packed
+        if packed is not None and (append_at is not None or save is not None):
+            raise ValueError('_query_rows: a packed cache is read-only and has no backward pass: unpack() first')
+        if packed == 'e4m3' and (n_context is None or self.precision != 'bf16'):
+            raise ValueError('_query_rows: an e4m3 cache takes the length route of the bf16 arm')
         fork = cache.forked()
         if fork:                                                             # lengths and positions are logical: own view = logical - split
             if n_context is None:
@@ -517,6 +623,11 @@ class MIGT:
                 ops.attn_prefix_fork(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], pkv[:, 2 * d:], pkv[:, :d], *own, att, B, H, Cp, room, N, L,
                                      3 * d, 3 * d, 3 * d, 3 * d, 3 * d, Cp * L * 3 * d, 3 * d, 3 * d, room * L * 3 * d, d, n_context,
                                      cache._split_dev, cache.share, bf16=self.precision == 'bf16')
+            elif packed == 'kv':                                             # ckv: (K, V), each [B*C*L, d] — the source cache's values, its bits
+                ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[0], ckv[1], att, B, H, C, N, L,
+                                3 * d, 3 * d, 3 * d, d, d, C * L * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
+            elif packed == 'e4m3':                                           # ckv: (kq, vq, kscale, vscale), tight tiles
+                ops.attn_prefix_q8(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], *ckv, att, B, H, C, N, L, 3 * d, 3 * d, 3 * d, d, n_context)
             else:
                 ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
                                 3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
@@ -731,6 +842,7 @@ class MIGT:
             raise TypeError(f'{what}: a ContextCache from prefill_context expected')
         if cache.forked():
             raise ValueError(f'{what}: the backward pass has no fork arm: pass cache.materialize() instead of the forked cache')
+        self._refuse_packed(cache, what)
         B, tshape = cache.B, cache.tshape
         L = int(np.prod(tshape))
         self._check_render_shapes(L)
@@ -956,6 +1068,7 @@ class MIGT:
         """the refusals ``append_to_context`` and ``rollout_from_context`` share, before any launch -> (cameras on the device, L)"""
         if not isinstance(cache, ContextCache):
             raise TypeError(f'{what}: a ContextCache from prefill_context expected')
+        self._refuse_packed(cache, what)
         L = int(np.prod(cache.tshape))
         self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
         cache.check(self)
@@ -1013,6 +1126,7 @@ class MIGT:
         from .render import plan_fork
         if cache.forked():
             raise ValueError('fork: a fork of a fork is not supported: fork cache.materialize() instead')
+        self._refuse_packed(cache, 'fork')
         L = int(np.prod(cache.tshape))
         self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
         cache.check(self)
@@ -1040,6 +1154,7 @@ class MIGT:
 
     def _materialize(self, cache):
         cache.check(self)
+        self._refuse_packed(cache, 'materialize')
         d, L, dev = self.config.d_model, int(np.prod(cache.tshape)), self.device
         B = cache.B
         out = cache.alias()
@@ -1072,6 +1187,8 @@ class MIGT:
         from .render import choose_best, plan_fork_lengths
         if not isinstance(parent, ContextCache) or not isinstance(child, ContextCache):
             raise TypeError('adopt_from_fork: two ContextCaches expected')
+        self._refuse_packed(parent, 'adopt_from_fork')
+        self._refuse_packed(child, 'adopt_from_fork')
         if not child.forked() or parent.forked():
             raise ValueError('adopt_from_fork: a plain parent cache and a cache forked from it expected')
         if child._parent is None or child._parent() is not parent:

@@ -695,6 +695,61 @@ def kv_append(qkv, cache, B, K, L, d, ld_src, ld_dst, cache_stride, capacity, po
     return cache
 
 
+def _pack_strides(C, H, q_view_stride, q_scene_stride, s_view_stride, s_scene_stride):
+    """the tight packed layout [B*C, H, 64, 64] bytes / [B*C, H] scales where a stride is None"""
+    qv = H * 4096 if q_view_stride is None else int(q_view_stride)
+    sv = H if s_view_stride is None else int(s_view_stride)
+    return (qv, C * qv if q_scene_stride is None else int(q_scene_stride), sv, C * sv if s_scene_stride is None else int(s_scene_stride))
+
+
+def kv_pack_e4m3(cache, kq, vq, kscale, vscale, B, C, H, L, ld_src, cache_stride, lengths, q_view_stride=None, q_scene_stride=None,
+                 s_view_stride=None, s_scene_stride=None):
+    """Pack the K and V thirds of a context cache buffer to e4m3 tiles with one power-of-two scale per (scene, view, head)
+    (csrc/kv_pack.hip): ``cache`` bf16 or fp32, ``C`` views of L rows per scene with leading dimension ``ld_src`` >= 3 * 64 H, thirds
+    (V, Q, K), scenes ``cache_stride`` elements apart -> ``kq`` uint8 tiles [64 keys][64 features], ``vq`` uint8 tiles [64 features][64 keys]
+    (tile (b, c, h) at byte b * q_scene_stride + c * q_view_stride + h * 4096; default: tight [B*C, H, 64, 64]) and ``kscale`` / ``vscale``
+    fp32 (element b * s_scene_stride + c * s_view_stride + h; default: tight [B*C, H]).  ``lengths``: int32 device tensor [B]; views at or
+    beyond a scene's length are neither read nor written.  One launch."""
+    if cache.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'kv_pack_e4m3: a bf16 or fp32 cache expected, got {cache.dtype}')
+    _chk(cache, cache.dtype, 'cache')
+    _chk(kq, torch.uint8, 'kq')
+    _chk(vq, torch.uint8, 'vq')
+    _chk(kscale, torch.float32, 'kscale')
+    _chk(vscale, torch.float32, 'vscale')
+    _chk(lengths, torch.int32, 'lengths')
+    if lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError(f'kv_pack_e4m3: lengths int32 [B = {B}] contiguous expected, got {tuple(lengths.shape)}')
+    qv, qs, sv, ss = _pack_strides(C, H, q_view_stride, q_scene_stride, s_view_stride, s_scene_stride)
+    check(_lib.load().vf_kv_pack_e4m3(_p(cache), cache.element_size(), _p(kq), _p(vq), _p(kscale), _p(vscale), B, C, H, L, ld_src, cache_stride,
+                                      qv, qs, sv, ss, _p(lengths), _stream()), 'vf_kv_pack_e4m3')
+    return kq, vq, kscale, vscale
+
+
+def attn_prefix_q8(q, k, v, kq, vq, kscale, vscale, out, B, H, C, N, L, ldq, ldk, ldv, ldo, ctx_len, q_view_stride=None, q_scene_stride=None,
+                   s_view_stride=None, s_scene_stride=None, dh=64):
+    """``attn_prefix(bf16=True, ctx_len=...)`` over a cache packed by ``kv_pack_e4m3`` (vf_attn_prefix_q8_bf16): ``kq`` / ``vq`` uint8
+    tiles and ``kscale`` / ``vscale`` fp32 with the strides as there, ``C`` views of room per scene; q / k / v bf16 or fp32 (one dtype),
+    ``out`` bf16 or fp32, ``ctx_len`` int32 device [B*N].  A view gets the bits of ``attn_prefix`` on the dequantised cache."""
+    lib = _lib.load()
+    _chk(ctx_len, torch.int32, 'ctx_len')
+    if ctx_len.numel() != B * N or not ctx_len.is_contiguous():
+        raise ValueError(f'attn_prefix_q8: ctx_len int32 [B*N = {B * N}] contiguous expected, got {tuple(ctx_len.shape)}')
+    o16 = out.dtype == torch.bfloat16
+    i16 = q.dtype == torch.bfloat16
+    for t in (q, k, v):
+        _chk(t, torch.bfloat16 if i16 else torch.float32, 'q/k/v')
+    _chk(kq, torch.uint8, 'kq')
+    _chk(vq, torch.uint8, 'vq')
+    _chk(kscale, torch.float32, 'kscale')
+    _chk(vscale, torch.float32, 'vscale')
+    qv, qs, sv, ss = _pack_strides(C, H, q_view_stride, q_scene_stride, s_view_stride, s_scene_stride)
+    check(lib.vf_attn_prefix_q8_bf16(_p(q), _p(k), _p(v), _p(kq), _p(vq), _p(kscale), _p(vscale), 1 if i16 else 0, _p(out if o16 else _f32(out)),
+                                     1 if o16 else 0, B, H, C, N, L, dh, ldq, ldk, ldv, qv, qs, sv, ss, ldo, _p(ctx_len), _stream()),
+          'vf_attn_prefix_q8_bf16')
+    return out
+
+
 def attn_spatial_supported(HW, C):
     return (HW, C) in ((256, 256), (64, 512), (64, 256))
 

@@ -172,6 +172,22 @@ def plan_capacity(capacity: int, needed: int) -> int:
     return capacity if needed <= capacity else max(2 * capacity, needed)
 
 
+def plan_cache_bytes(B: int, C: int, L: int, d_model: int, n_head: int, n_layer: int, elem_bytes: int, form=None) -> int:
+    """The bytes of a context cache of B scenes x C views of room, from its shapes (``ContextCache.nbytes``): ``form`` None = the plain
+    cache ([B*C*L, 3 d] per layer), 'kv' = the K/V-only pack ([B*C*L, d] twice: exactly 2/3), 'e4m3' = the e4m3 pack (two byte tiles
+    [B*C, H, 64, 64] and two fp32 scales [B*C, H] per layer; ``elem_bytes`` does not enter).  Pure."""
+    B, C, L, d, H, n = int(B), int(C), int(L), int(d_model), int(n_head), int(n_layer)
+    if min(B, C, L, d, H, n) < 0 or int(elem_bytes) not in (2, 4):
+        raise ValueError(f'plan_cache_bytes: sizes >= 0 and elem_bytes 2 or 4 expected, got {(B, C, L, d, H, n, elem_bytes)}')
+    if form is None:
+        return n * B * C * L * 3 * d * int(elem_bytes)
+    if form == 'kv':
+        return n * 2 * B * C * L * d * int(elem_bytes)
+    if form == 'e4m3':
+        return n * 2 * (B * C * H * 64 * 64 + B * C * H * 4)
+    raise ValueError(f"plan_cache_bytes: form None, 'kv' or 'e4m3' expected, got {form!r}")
+
+
 def plan_rollout_lengths(lengths, T: int):
     """Context lengths of a T-step roll-out from scenes of ``lengths`` [B] filled views: (gen int32 [T,B], pair int32 [T,B,2]).
     ``gen[t, b] = lengths[b] + t``: what the MASK view of step t sees (the context and the generated views 0 ... t-1), and also the
@@ -297,6 +313,34 @@ class ViewRenderer:
         self.transform, self.context_codes, self.n_context = transform, codes, n_context
         return self
 
+    def pack(self, dtype=None):
+        """Pack the context in place (``ContextCache.pack``; the plain cache is released) and return ``self``: ``dtype=None`` keeps the
+        K and V thirds as they are (2/3 of the bytes, both arms, every answer keeps its bits), ``dtype='e4m3'`` (bf16 models) stores
+        them as e4m3 bytes with a power-of-two scale per (scene, view, head) — about 1/3 of the bf16 bytes, the answers of the bf16 arm
+        on the dequantised cache.  ``render``, ``sample``, ``score``, ``localize`` and ``sweep`` go on working; ``append``, ``rollout``,
+        ``fork``, ``score_gradient`` and ``refine`` refuse until ``unpack()``."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.pack: set_context() first')
+        self.cache = self.cache.pack(dtype)
+        return self
+
+    def unpack(self):
+        """Undo ``pack``: a plain cache again (the K/V-only form bit for bit, the e4m3 form dequantised; the Q third zeros), in place."""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.unpack: set_context() first')
+        self.cache = self.cache.unpack()
+        return self
+
+    def context_bytes(self):
+        """the bytes of the context cache's own tensors, from their shapes"""
+        if self.cache is None:
+            raise RuntimeError('ViewRenderer.context_bytes: set_context() first')
+        return self.cache.nbytes()
+
+    def _refuse_packed(self, what):
+        if self.cache.packed is not None:
+            raise ValueError(f'ViewRenderer.{what}: the context is packed ({self.cache.packed!r}) and read-only: unpack() first')
+
     def _own_lengths(self, cache):
         """before the context grows: a ragged batch's valid views (``set_context(n_context=...)``) become the cache's own lengths, so
         that new views go behind each scene's valid views (over its padding)"""
@@ -325,6 +369,7 @@ class ViewRenderer:
         ``sample``, ``score``, ``localize`` and ``sweep`` sees the grown context; ``n_context`` and ``context_codes`` follow."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.append: set_context() first')
+        self._refuse_packed('append')
         if cameras is None or (images is None) == (codes is None):
             raise ValueError('append: cameras and exactly one of images / codes expected')
         tm, cm = self.transformer, self.codebook
@@ -360,6 +405,7 @@ class ViewRenderer:
         ``refine`` need ``cache.materialize()``."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.fork: set_context() first')
+        self._refuse_packed('fork')
         if isinstance(S, bool) or int(S) != S or int(S) < 1:
             raise ValueError(f'fork: S, an integer >= 1, expected, got {S}')
         S = int(S)
@@ -391,6 +437,7 @@ class ViewRenderer:
         ``context_codes`` and ``n_context`` follow as with ``keep=True`` for S = 1, and the result gains ``adopted`` int64 [B]."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.rollout: set_context() first')
+        self._refuse_packed('rollout')
         if adopt is not None and not (fork and int(n_samples) > 1):
             raise ValueError('rollout: adopt goes with fork=True and n_samples > 1 (keep=True keeps the one trajectory of n_samples = 1)')
         if adopt is not None and isinstance(adopt, str) and adopt != 'best':
@@ -635,6 +682,7 @@ class ViewRenderer:
         chunking."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.score_gradient: set_context() first')
+        self._refuse_packed('score_gradient')
         if self.cache.forked():
             raise ValueError('ViewRenderer.score_gradient: the backward pass has no fork arm: set the cache to cache.materialize() first')
         query_cameras = self._world_cameras('score_gradient', query_cameras)
@@ -662,6 +710,7 @@ class ViewRenderer:
         ``return_trace`` trace fp32 [steps+1,B,N]).  N is walked in chunks of whole views; views are refined independently of each other."""
         if self.cache is None:
             raise RuntimeError('ViewRenderer.refine: set_context() first')
+        self._refuse_packed('refine')
         if self.cache.forked():
             raise ValueError('ViewRenderer.refine: the backward pass has no fork arm: set the cache to cache.materialize() first')
         B = self.cache.B
