@@ -24,126 +24,11 @@ import torch
 from . import ops
 from . import geometry
 from .config import MIGTConfig
+from .context_cache import ContextCache                # noqa: F401  (tests and tools import it from here)
 
 
 class _Dense:
     __slots__ = ('wp', 'wp16', 'wp6', 'bias', 'k', 'n', 'w_raw')
-
-
-class ContextCache:
-    """Keys and values of C context views in every layer (MIGT.prefill_context): ``kv[i]`` is layer i's fused c_attn output
-    [B*capacity*L, 3*d_model] with thirds (V, Q, K).  Valid for the model object, weights, arithmetic arm and device that made it.
-    ``capacity`` >= C views of room per scene (``prefill_context(capacity=...)``, grown by ``append_to_context``); ``C`` = the number of
-    filled views, the maximum over scenes; ``lengths``: the filled views per scene, host int32 [B], or None for "all C".
-
-    A FORKED cache (``fork(S)``) has B*S scenes that read the parent's views where they lie and own only what they add:
-    ``parent_kv`` = the parent's per-layer tensors as they were at fork time (a list of its own: a parent that reallocates later keeps
-    the old buffers alive for the child), ``parent_capacity`` their views of room per scene, ``split`` host int32 [B*S] = the parent's
-    filled length per child scene at fork time, ``share`` = S (child scene b reads parent scene b // S), ``room`` = own views of room
-    per child scene, and ``kv[i]`` the OWN buffers [B*S*room*L, 3*d_model].  ``filled()``, ``lengths``, ``C`` and ``capacity`` count
-    LOGICAL views: logical view s of scene b is parent view s below ``split[b]``, own view ``s - split[b]`` otherwise
-    (``render.map_fork_views``).  Every child holds the same number of own views.
-
-    A PACKED cache (``pack()``) is read-only and holds no Q third: ``packed`` is ``'kv'`` — ``kv[i]`` = (K, V), two
-    contiguous [B*C*L, d_model] tensors in the cache's dtype, served by the plain prefix attention with the bits of the source cache —
-    or ``'e4m3'`` (bf16 arm) — ``kv[i]`` = (kq uint8 [B*C, H, 64 keys, 64 features], vq uint8 [B*C, H, 64 features, 64 keys], kscale,
-    vscale fp32 [B*C, H]): OCP e4m3 bytes with one power-of-two scale per (scene, view, head), served by ``ops.attn_prefix_q8`` with the
-    bits of the bf16 arm on the dequantised cache (``unpack()``).  Both are tight (``capacity`` = ``C``, the longest scene)."""
-    _FIELDS = ('kv', 'B', 'C', 'tshape', 'device', 'arm', 'act16', 'qkv16', '_owner', '_weights', 'capacity', 'lengths',
-               'parent_kv', 'parent_capacity', 'split', 'share', 'room', '_parent', '_split_dev', 'packed')
-    __slots__ = _FIELDS + ('__weakref__',)
-
-    def __init__(self, model, kv, B, C, tshape, capacity=None, lengths=None):
-        import weakref
-        self.parent_kv = self.parent_capacity = self.split = self.share = self.room = self._parent = self._split_dev = None
-        self.packed = None
-        self.kv, self.B, self.C, self.tshape = kv, B, C, tuple(tshape)
-        self.capacity = C if capacity is None else int(capacity)
-        self.lengths = None if lengths is None else np.array(lengths, dtype=np.int32).reshape(B)
-        self.device = model.device
-        self.arm = (model.precision, model.dense_arith, model.attention)
-        self.act16, self.qkv16 = model._act_dtypes()
-        self._owner = weakref.ref(model)
-        self._weights = model._weights_version
-
-    def filled(self):
-        """the filled views per scene, int32 [B] (host; a copy)"""
-        return np.full(self.B, self.C, dtype=np.int32) if self.lengths is None else self.lengths.copy()
-
-    def ragged(self):
-        """True where the fixed-C attention entry would read unfilled rows: the cache has slack, or lengths of its own"""
-        return self.capacity != self.C or self.lengths is not None
-
-    def alias(self):
-        """A second ContextCache on the SAME buffers with lengths of its own: what is appended through it lies beyond this cache's lengths
-        (and moves to new buffers, leaving these, once the capacity is exceeded)."""
-        c = object.__new__(ContextCache)
-        for s in self._FIELDS:
-            setattr(c, s, getattr(self, s))
-        c.kv = list(self.kv)
-        c.lengths = None if self.lengths is None else self.lengths.copy()
-        if self.forked():
-            c.parent_kv = list(self.parent_kv)
-        return c
-
-    def forked(self):
-        """True for a cache made by ``fork``: two segments per scene, the parent's and its own"""
-        return self.share is not None
-
-    def _model(self, what):
-        m = self._owner()
-        if m is None:
-            raise ValueError(f'ContextCache.{what}: the model that filled this cache is gone')
-        self.check(m)
-        return m
-
-    def fork(self, S, room=None):
-        """S children per scene that share this cache's views and own only what they add: a forked ContextCache of B*S scenes, scene b's
-        children at b*S ... b*S+S-1 (the order of ``render.plan_replication``), each starting at this cache's filled length of scene b.
-        ``room``: own views of room per child (None: 0, allocated at the first append; grown by doubling, own buffers only).  Nothing of
-        this cache is copied, written or run again, and nothing appended to it later — behind its lengths of now — reaches a child.
-        ``generate`` / ``sample`` / ``score`` / ``localize_from_context``, ``append_to_context`` and ``rollout_from_context`` take the
-        fork as any cache, with the bits of the materialised cache; ``score_grad_from_context`` and ``refine_from_context`` need
-        ``materialize()``.  A fork of a fork is refused: ``materialize()`` it first."""
-        return self._model('fork')._fork(self, S, room)
-
-    def materialize(self):
-        """A plain ContextCache of this fork's B*S scenes in buffers of its own: the parent's views at position 0, the own views behind
-        them, copied bit for bit by ``ops.kv_append`` (every result on it has the fork's bits).  On a plain cache: a copy."""
-        return self._model('materialize')._materialize(self)
-
-    def pack(self, dtype=None):
-        """A packed, READ-ONLY ContextCache of the same scenes in buffers of its own (this cache is left untouched), tight (capacity =
-        the longest scene), lengths kept.  ``dtype=None``: the K and V thirds only, in the cache's dtype — 2/3 of the bytes, both arms,
-        every result ``torch.equal`` to this cache's.  ``dtype='e4m3'`` (``precision='bf16'`` models only): OCP e4m3 bytes with one
-        power-of-two scale per (scene, view, head) for K and one for V (``ops.kv_pack_e4m3``) — about 1/3 of the bf16 bytes; every
-        result has the bits of the bf16 arm on ``unpack()``'s dequantised cache, and what is lost is the quantisation alone.
-        ``generate`` / ``sample`` / ``score`` / ``localize_from_context`` take a packed cache as any cache; whatever grows a cache, forks
-        it or differentiates through it refuses it: ``unpack()`` first.  A fork or a packed cache is refused: ``materialize()`` /
-        ``unpack()`` first."""
-        return self._model('pack')._pack(self, dtype)
-
-    def unpack(self):
-        """A plain ContextCache (thirds V, Q, K) of a packed one, in buffers of its own: the K and V thirds bit for bit (K/V-only form)
-        or dequantised (e4m3 form: e4m3 * scale, exact in bf16), the Q third zeros — the way back to ``append_to_context``,
-        ``rollout_from_context``, ``fork`` and the gradients.  On a cache that is not packed: refused."""
-        return self._model('unpack')._unpack(self)
-
-    def nbytes(self):
-        """the bytes of this cache's own tensors, from their shapes (a fork: its own buffers, not the parent's)"""
-        n = 0
-        for t in self.kv:
-            for x in (t if isinstance(t, (tuple, list)) else (t,)):
-                n += x.numel() * x.element_size()
-        return n
-
-    def check(self, model):
-        if self._owner() is not model or self._weights != model._weights_version:
-            raise ValueError('ContextCache belongs to another model (or to weights that have been replaced since): prefill again')
-        if self.arm != (model.precision, model.dense_arith, model.attention) or (self.act16, self.qkv16) != model._act_dtypes():
-            raise ValueError(f'ContextCache was filled on the {self.arm} arm, the model now runs {(model.precision, model.dense_arith, model.attention)}')
-        if self.device != model.device:
-            raise ValueError(f'ContextCache lives on {self.device}, the model on {model.device}')
 
 
 class MIGT:
@@ -444,116 +329,20 @@ class MIGT:
         self._blocks(codes, self._pose_embed(cameras), B, C, L, kv_sink=kv)
         cache = ContextCache(self, kv, B, C, tshape)
         if capacity is not None and int(capacity) > C:                     # (capacity = C is the tight cache: nothing to move)
-            self._reallocate(cache, int(capacity))
+            cache.reallocate(int(capacity))
         return cache
 
-    def _reallocate(self, cache, capacity):
-        """new buffers of ``capacity`` views per scene inside the same ContextCache: every layer's cached views (the V and K thirds of all
-        ``cache.capacity`` views of every scene) copied bit for bit by one ``ops.kv_append`` at position 0"""
-        d, L = self.config.d_model, int(np.prod(cache.tshape))
-        B, old = cache.B, cache.capacity
-        pos0 = torch.zeros(B, dtype=torch.int32, device=self.device)
-        if cache.forked():                                                   # a fork grows its OWN buffers only: the parent's stay where they lie
-            room = capacity - int(cache.split.max())
-            for i, src in enumerate(cache.kv):
-                dst = torch.empty((B * room * L, 3 * d), dtype=src.dtype, device=self.device)
-                if cache.room:
-                    ops.kv_append(src, dst, B, cache.room, L, d, 3 * d, 3 * d, room * L * 3 * d, room, pos0)
-                cache.kv[i] = dst
-            cache.room, cache.capacity = room, capacity
-            return
-        for i, src in enumerate(cache.kv):
-            dst = torch.empty((B * capacity * L, 3 * d), dtype=src.dtype, device=self.device)
-            ops.kv_append(src, dst, B, old, L, d, 3 * d, 3 * d, capacity * L * 3 * d, capacity, pos0)
-            cache.kv[i] = dst
-        cache.capacity = capacity
-
-    # ------------------------------------------------------------------ packed, read-only caches (DESIGN.md §6.20)
-    @staticmethod
-    def _refuse_packed(cache, what):
-        if cache.packed is not None:
-            raise ValueError(f'{what}: a packed cache is read-only (it holds no Q third and has no room): pass cache.unpack() instead')
-
-    def _pack(self, cache, dtype):
-        if cache.forked():
-            raise ValueError('pack: a forked cache reads two segments: pack cache.materialize() instead')
-        if cache.packed is not None:
-            raise ValueError(f'pack: this cache is packed already ({cache.packed!r}): pack cache.unpack() instead')
-        if dtype is not None and dtype != 'e4m3':
-            raise ValueError(f"pack: dtype None (the K and V thirds as they are) or 'e4m3' expected, got {dtype!r}")
-        if dtype == 'e4m3' and self.precision != 'bf16':
-            raise ValueError(f"pack: dtype='e4m3' is for precision='bf16' models; the {self.precision!r} arm exists for exactness: "
-                             'pack(dtype=None) keeps its bits')
-        L = int(np.prod(cache.tshape))
-        self._check_render_shapes(L)
-        c, dev = self.config, self.device
-        d, H, B, C, cap = c.d_model, c.n_head, cache.B, cache.C, cache.capacity
-        out = cache.alias()
-        out.lengths = cache.filled() if cache.ragged() else None                 # the length route whenever the source takes it
-        out.capacity = C
-        if dtype is None:
-            out.packed = 'kv'
-            out.kv = [tuple(kv.view(B, cap * L, 3 * d)[:, :C * L, a:a + d].contiguous().view(B * C * L, d) for a in (2 * d, 0)) for kv in cache.kv]
-            return out
-        out.packed = 'e4m3'
-        lengths = torch.from_numpy(cache.filled()).to(dev)
-        kvs = []
-        for kv in cache.kv:
-            kq = torch.zeros((B * C, H, 64, 64), dtype=torch.uint8, device=dev)
-            vq = torch.zeros((B * C, H, 64, 64), dtype=torch.uint8, device=dev)
-            ks = torch.ones((B * C, H), dtype=torch.float32, device=dev)
-            vs = torch.ones((B * C, H), dtype=torch.float32, device=dev)
-            if B and C:
-                ops.kv_pack_e4m3(kv, kq, vq, ks, vs, B, C, H, L, 3 * d, cap * L * 3 * d, lengths)
-            kvs.append((kq, vq, ks, vs))
-        out.kv = kvs
-        return out
-
-    def _unpack(self, cache):
-        if cache.packed is None:
-            raise ValueError('unpack: a packed cache (ContextCache.pack) expected')
-        c, dev = self.config, self.device
-        d, H, B, C = c.d_model, c.n_head, cache.B, cache.C
-        L = int(np.prod(cache.tshape))
-        out = cache.alias()
-        out.packed = None
-        dt = torch.bfloat16 if cache.qkv16 else torch.float32
-        kvs = []
-        if cache.packed == 'e4m3':                                           # byte -> value through the 256 e4m3 numbers (exact), times the tile's scale
-            lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(dev)
-        for t in cache.kv:
-            kv = torch.zeros((B * C * L, 3 * d), dtype=dt, device=dev)
-            if cache.packed == 'kv':
-                kv[:, 2 * d:], kv[:, :d] = t[0], t[1]
-            else:
-                kq, vq, ks, vs = t
-                k = lut[kq.long()] * ks.view(B * C, H, 1, 1)                 # [B*C, H, key, feature]
-                v = lut[vq.long()] * vs.view(B * C, H, 1, 1)                 # [B*C, H, feature, key]
-                kv[:, 2 * d:] = k.permute(0, 2, 1, 3).reshape(B * C * L, d).to(dt)
-                kv[:, :d] = v.permute(0, 3, 1, 2).reshape(B * C * L, d).to(dt)
-            kvs.append(kv)
-        out.kv = kvs
-        return out
-
     def _context_lengths(self, cache, n_context, N):
-        """``n_context`` of the four ``*_from_context`` methods -> int32 device tensor [B*N] for ``_query_rows``, or None (None in, on a
+        """``n_context`` of the ``*_from_context`` methods -> int32 device tensor [B*N] for ``_query_rows``, or None (None in, on a
         cache without slack and without lengths of its own: every view sees all C cached views, the path and the launches without the
         keyword; a cache with slack or lengths always takes the length route, and its default lengths are its own: the fixed-C entry
         would read unfilled rows).  An int, [B] (one length per scene) or [B,N] (one per query view) of integers in [0, the filled length
         of the scene]: the view sees that many leading context views and itself, which is the model's answer for that context (0: no
         context at all).  Host data preferred (a device tensor is brought to the host once, to validate it); anything else: ValueError,
-        before any launch.  A group of 4 (bf16) / 2 (f32) consecutive views costs what its longest member costs, and rows are not
-        reordered here."""
-        from .render import plan_context_lengths
-        if n_context is None:
-            if not cache.ragged() and cache.packed != 'e4m3':                # (the e4m3 attention is a length kernel: its default lengths are all C)
-                return None
-            plan = plan_context_lengths(cache.filled(), cache.B, N, cache.C)
-        else:
-            plan = plan_context_lengths(n_context, cache.B, N, cache.C)
-            if cache.lengths is not None and plan.size and (plan > cache.lengths.reshape(cache.B, 1)).any():
-                raise ValueError(f'n_context: at most the filled views of each scene ({cache.lengths.tolist()}) expected, got {plan.max(1).tolist()}')
-        return torch.from_numpy(plan.reshape(-1)).to(self.device)
+        before any launch (``ContextCache.plan_lengths``).  A group of 4 (bf16) / 2 (f32) consecutive views costs what its longest
+        member costs, and rows are not reordered here."""
+        plan = cache.plan_lengths(n_context, N)
+        return None if plan is None else torch.from_numpy(plan.reshape(-1)).to(self.device)
 
     def _query_rows(self, cache, ids32, add, N, n_context=None, append_at=None, tail='all', save=None):
         """The per-layer loop over the rows of N query views per scene of ``cache``: ``ids32`` int32 [B*N*L] token ids, ``add`` fp32
@@ -573,30 +362,17 @@ class MIGT:
         needs (``score_grad_from_context``): per layer the tuple (the block's input h, the residual stream after the attention, the
         layer's fused c_attn output in a buffer of its own, the LayerNorm-2 output), then the final h that ``ln_f`` reads.  Same launches
         on the same values: the hidden states keep their bits.  With ``tail='all'`` only.
-        A forked cache (``ContextCache.fork``) takes the fork route here and nowhere else: ``ops.attn_prefix_fork`` over the parent's
-        buffers and the own ones, and ``append_at`` (logical) writes the own buffers at ``append_at - split``.
-        A packed cache (``ContextCache.pack``) takes its routes here and nowhere else: the K/V-only form the same ``ops.attn_prefix`` on
-        its two tight tensors (leading dimension d), the e4m3 form ``ops.attn_prefix_q8``; it is read-only (no ``append_at``, no ``save``)."""
+        The cache's form (plain, forked, packed) is the cache's own business: ``plan_pass`` refuses what the form cannot serve before
+        any launch, ``append`` and ``attend`` issue the form's launch (viewformer_amd/context_cache.py)."""
         c, dev = self.config, self.device
-        B, C = cache.B, cache.capacity                                       # the attention's C is the room: lengths say what is filled
         if save is not None and tail != 'all':
             raise ValueError('_query_rows: save goes with tail="all" (a backward pass needs every row)')
-        L = int(np.prod(cache.tshape))
-        d, H, nE = c.d_model, c.n_head, c.n_embeddings
+        B, L = cache.B, cache.L
+        d, nE = c.d_model, c.n_embeddings
         M = B * N * L
         if append_at is not None and n_context is None:
             raise ValueError('_query_rows: appended views carry their context lengths')
-        packed = cache.packed
-        if packed is not None and (append_at is not None or save is not None):
-            raise ValueError('_query_rows: a packed cache is read-only and has no backward pass: unpack() first')
-        if packed == 'e4m3' and (n_context is None or self.precision != 'bf16'):
-            raise ValueError('_query_rows: an e4m3 cache takes the length route of the bf16 arm')
-        fork = cache.forked()
-        if fork:                                                             # lengths and positions are logical: own view = logical - split
-            if n_context is None:
-                raise ValueError('_query_rows: a forked cache takes the length route')
-            Cp, room = cache.parent_capacity, cache.room
-            own_at = None if append_at is None else append_at - cache._split_dev
+        at = cache.plan_pass(n_context, append_at, save)
         h = ops.embed_sum(ids32, self._wte, self._wpe, add, B * N, L, d, nE + 2)           # migt.py:392
         act16, qkv16 = cache.act16, cache.qkv16
         att = torch.empty((M, d), dtype=torch.bfloat16 if act16 else torch.float32, device=dev)
@@ -609,28 +385,11 @@ class MIGT:
                 qkv = torch.empty_like(qkv)                                  # the backward reads every layer's q / k / v again
             h_in = h
             self._dense_launch(a, self._dense[p + '.attn.c_attn'], M, qkv)
-            ckv = cache.kv[i]                                                # [B*capacity*L, 3d], thirds (V, Q, K)
             if append_at is not None:
-                if fork:                                                     # ckv: the OWN buffer [B*room*L, 3d]
-                    ops.kv_append(qkv, ckv, B, N, L, d, 3 * d, 3 * d, room * L * 3 * d, room, own_at)
-                else:
-                    ops.kv_append(qkv, ckv, B, N, L, d, 3 * d, 3 * d, C * L * 3 * d, C, append_at)
+                cache.append(i, qkv, N, at)
             if last and tail is None:
                 return None                                                  # the last block's other launches feed nothing: the keys and values are in
-            if fork:
-                pkv = cache.parent_kv[i]                                     # [B/share*Cp*L, 3d], read where it lies
-                own = (ckv[:, 2 * d:], ckv[:, :d]) if room else (None, None)
-                ops.attn_prefix_fork(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], pkv[:, 2 * d:], pkv[:, :d], *own, att, B, H, Cp, room, N, L,
-                                     3 * d, 3 * d, 3 * d, 3 * d, 3 * d, Cp * L * 3 * d, 3 * d, 3 * d, room * L * 3 * d, d, n_context,
-                                     cache._split_dev, cache.share, bf16=self.precision == 'bf16')
-            elif packed == 'kv':                                             # ckv: (K, V), each [B*C*L, d] — the source cache's values, its bits
-                ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[0], ckv[1], att, B, H, C, N, L,
-                                3 * d, 3 * d, 3 * d, d, d, C * L * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
-            elif packed == 'e4m3':                                           # ckv: (kq, vq, kscale, vscale), tight tiles
-                ops.attn_prefix_q8(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], *ckv, att, B, H, C, N, L, 3 * d, 3 * d, 3 * d, d, n_context)
-            else:
-                ops.attn_prefix(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], att, B, H, C, N, L,
-                                3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, bf16=self.precision == 'bf16', ctx_len=n_context)
+            cache.attend(i, qkv, att, N, n_context)
             att_i = att
             if last and tail != 'all' and N > 1:
                 # the last block: only the returned view's rows go on (as _blocks' tail_views: the other views' rows feed nothing)
@@ -647,6 +406,52 @@ class MIGT:
             save.append(h)
         return ops.layernorm(h, *self._ln['ln_f'], M, d)                     # migt.py:408
 
+    def _context_args(self, what, cache, cameras=None, codes=None, n_context=None, one_photo=False, needs=None, view0=None, lengths=True):
+        """The front matter of every method that takes a cache, in ``score_from_context``'s order: the cache (a ContextCache that can do
+        what ``needs`` — None, ``'room'`` or ``'backward'`` —, of a shape and arm with prefix-cache attention, of this model), the optional
+        ``cameras`` fp32 [B,N,7], the optional ``codes`` int [B,N,t,t] (``one_photo``: or [B,1,t,t]), sample's ``view0`` and ``n_context``
+        -> (cameras and codes on the device, N, L, the context lengths as ``_context_lengths`` makes them, None without ``lengths``).
+        Every refusal comes before any launch and before the one host-to-device copy of the lengths."""
+        if not isinstance(cache, ContextCache):
+            raise TypeError(f'{what}: a ContextCache from prefill_context expected')
+        if needs is not None:
+            (cache.refuse_backward if needs == 'backward' else cache.refuse_packed)(what)
+        B, tshape, L = cache.B, cache.tshape, cache.L
+        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
+        cache.check(self)
+        N = None
+        if cameras is not None:
+            cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.device)
+            if cameras.dim() != 3 or cameras.shape[0] != B or cameras.shape[2] != 7:
+                raise ValueError(f'{what}: cameras [B={B},N,7] expected for this cache, got {tuple(cameras.shape)}')
+            N = cameras.shape[1]
+        if codes is not None:
+            codes = torch.as_tensor(codes).to(self.device)
+            if (codes.dim() != 2 + len(tshape) or codes.shape[0] != B or tuple(codes.shape[2:]) != tshape or codes.dtype.is_floating_point
+                    or codes.dtype == torch.bool or not (N is None or codes.shape[1] == N or (one_photo and codes.shape[1] == 1))):
+                raise ValueError(f'{what}: codes int [B={B},N={N}{" or 1" if one_photo else ""},{",".join(map(str, tshape))}] expected for this '
+                                 f'cache, got {codes.dtype} {tuple(codes.shape)}')
+            N = codes.shape[1] if N is None else N
+        if view0 is not None and (view0 < 0 or (view0 + N) * L >= 1 << 32):
+            raise ValueError(f'{what}: 0 <= view0 and (view0 + N) * {L} < 2^32 expected, got view0 = {view0}, N = {N}')
+        return cameras, codes, N, L, self._context_lengths(cache, n_context, N) if lengths else None
+
+    def _mask_rows(self, cameras, L):
+        """N MASK views per scene at ``cameras`` [B,N,7] -> (``ids32``, ``add``) for ``_query_rows``: the MASK token on every row, the
+        cameras' pose embedding per view"""
+        B, N = cameras.shape[:2]
+        add = self._pose_embed(cameras).contiguous().view(B * N, self.config.d_model)
+        return torch.full((B * N * L,), self.mask_token, dtype=torch.int32, device=self.device), add
+
+    @staticmethod
+    def _sampler_args(what, n_samples, temperature, top_k, top_p):
+        """the sampler's arguments as ``ops.sample_rows`` takes them, refused here before any launch -> n_samples as an int"""
+        if not 1 <= int(n_samples) <= 65535 or int(n_samples) != n_samples:
+            raise ValueError(f'{what}: 1 <= n_samples <= 65535 expected, got {n_samples}')
+        if not (float(temperature) > 0 and math.isfinite(float(temperature))) or not float(top_p) > 0 or int(top_k) < 0:
+            raise ValueError(f'{what}: temperature > 0 (finite), top_p > 0 and top_k >= 0 expected, got {temperature}, {top_p}, {top_k}')
+        return int(n_samples)
+
     def generate_from_context(self, cache, query_cameras, codes_only: bool = True, return_confidence: bool = False, n_context=None):
         """N novel views per scene from a prefilled context: ``query_cameras`` fp32 [B,N,7] in the context's (relative, normalised)
         frame -> generated code maps int64 [B,N,t,t], or with ``codes_only=False`` the logits [B,N,t,t,n_embeddings].  Every query is
@@ -657,31 +462,18 @@ class MIGT:
         code (max logit - lse) and the entropy of the token's distribution, from the same LM-head launch (``_lm_score``).
         ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
         keyword); consecutive views share an attention group, which costs what its longest member costs."""
-        if not isinstance(cache, ContextCache):
-            raise TypeError('generate_from_context: a ContextCache from prefill_context expected')
         if return_confidence and not codes_only:
             raise ValueError('generate_from_context: return_confidence goes with codes_only=True (the logits say it all)')
-        cache.check(self)
-        c, dev = self.config, self.device
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
-        B, C, tshape = cache.B, cache.C, cache.tshape
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
-            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
-        N = query_cameras.shape[1]
-        L = int(np.prod(tshape))
-        self._check_render_shapes(L)
-        d, H, nE = c.d_model, c.n_head, c.n_embeddings
+        query_cameras, _, N, L, ctx = self._context_args('generate_from_context', cache, query_cameras, n_context=n_context)
+        dev, nE, B, tshape = self.device, self.config.n_embeddings, cache.B, cache.tshape
         M = B * N * L
-        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             if return_confidence:
                 return (torch.empty((B, 0, *tshape), dtype=torch.int64, device=dev), torch.empty((B, 0, *tshape), dtype=torch.float32, device=dev),
                         torch.empty((B, 0, *tshape), dtype=torch.float32, device=dev))
             return (torch.empty((B, 0, *tshape), dtype=torch.int64, device=dev) if codes_only
                     else torch.empty((B, 0, *tshape, nE), dtype=torch.float32, device=dev))
-        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
-        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
-        hf = self._query_rows(cache, ids32, add, N, ctx)
+        hf = self._query_rows(cache, *self._mask_rows(query_cameras, L), N, ctx)
         if return_confidence:
             st = self._lm_score(hf, M, want=('idx', 'max_logit', 'lse', 'entropy'))
             return st['idx'].view(B, N, *tshape), (st['max_logit'] - st['lse']).view(B, N, *tshape), st['entropy'].view(B, N, *tshape)
@@ -708,33 +500,16 @@ class MIGT:
         epilogue without the logits, the slower route on the MI355X, kept for A/B runs and tests).  A code outside [0, n_embeddings) has log-probability -inf.  Views are independent: a view's results do not depend on N.
         ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
         keyword); consecutive views share an attention group, which costs what its longest member costs."""
-        if not isinstance(cache, ContextCache):
-            raise TypeError('score_from_context: a ContextCache from prefill_context expected')
-        B, tshape = cache.B, cache.tshape
-        L = int(np.prod(tshape))
-        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
-        cache.check(self)
-        c, dev = self.config, self.device
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
-            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
-        N = query_cameras.shape[1]
-        codes = torch.as_tensor(codes).to(dev)
-        if (codes.dim() != 2 + len(tshape) or codes.shape[0] != B or codes.shape[1] not in (1, N) or tuple(codes.shape[2:]) != tshape
-                or codes.dtype.is_floating_point or codes.dtype == torch.bool):
-            raise ValueError(f'codes int [B={B},N={N} or 1,{",".join(map(str, tshape))}] expected, got {codes.dtype} {tuple(codes.shape)}')
-        d = c.d_model
+        query_cameras, codes, N, L, ctx = self._context_args('score_from_context', cache, query_cameras, codes, n_context, one_photo=True)
+        dev, B, tshape = self.device, cache.B, cache.tshape
         M = B * N * L
-        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             e4 = lambda dt: torch.empty((B, 0, *tshape), dtype=dt, device=dev)
             e2 = lambda: torch.empty((B, 0), dtype=torch.float32, device=dev)
             return dict(token_log_prob=e4(torch.float32), log_likelihood=e2(), predicted_codes=e4(torch.int64), confidence=e4(torch.float32),
                         entropy=e4(torch.float32), accuracy=e2())
         target = codes.to(torch.int32).expand(B, N, *tshape).reshape(M).contiguous()
-        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
-        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
-        hf = self._query_rows(cache, ids32, add, N, ctx)
+        hf = self._query_rows(cache, *self._mask_rows(query_cameras, L), N, ctx)
         st = self._lm_score(hf, M, target, fused=fused)
         tlp, conf, ll, acc = ops.score_views(st, target, B * N, L)           # log-likelihood: one fp32 chain per view, in token order
         return dict(token_log_prob=tlp.view(B, N, *tshape), log_likelihood=ll.view(B, N), predicted_codes=st['idx'].view(B, N, *tshape),
@@ -794,9 +569,8 @@ class MIGT:
         (DESIGN.md §6.16), so the gradient stops there; weight gradients go to scratch and are dropped."""
         from . import train_ops as T
         c, dev = self.config, self.device
-        B, C = cache.B, cache.capacity
-        L = int(np.prod(cache.tshape))
-        d, H, nE = c.d_model, c.n_head, c.n_embeddings
+        B, L = cache.B, cache.L
+        d, nE = c.d_model, c.n_embeddings
         M = B * N * L
         dgam, dbet = torch.empty(d, dtype=torch.float32, device=dev), torch.empty(d, dtype=torch.float32, device=dev)
         # + log-likelihood: dlogits = onehot - softmax = (softmax - onehot) * (-1).  A code outside [0, n_embeddings) has log-probability
@@ -814,10 +588,8 @@ class MIGT:
             dm = self._linear_dx(p + '.mlp.c_fc', T.gelu_bwd(u, df), M)
             dh = T.layernorm_bwd(dm, h_mid, self._ln[p + '.ln_2'][0], dgam, dbet, M, d, accumulate=False, res=dh)
             datt = self._linear_dx(p + '.attn.c_proj', dh, M)
-            ckv = cache.kv[i]
             dqkv = torch.empty((M, 3 * d), dtype=torch.float32, device=dev)
-            ops.attn_prefix_bwd(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], ckv[:, 2 * d:], ckv[:, :d], datt, dqkv, B, H, C, N, L,
-                                3 * d, 3 * d, 3 * d, 3 * d, 3 * d, C * L * 3 * d, d, 3 * d, ctx_len=ctx)
+            cache.attend_backward(i, qkv, datt, dqkv, N, ctx)
             da = self._linear_dx(p + '.attn.c_attn', dqkv, M)
             dh = T.layernorm_bwd(da, h_in, self._ln[p + '.ln_1'][0], dgam, dbet, M, d, accumulate=False, res=dh)
         dwte = torch.empty((nE + 2, d), dtype=torch.float32, device=dev)
@@ -838,41 +610,20 @@ class MIGT:
     def _score_grad_args(self, what, cache, query_cameras, codes, n_context):
         """``score_from_context``'s validation, in its order -> (cameras and codes on the device, N, the context lengths as
         ``_context_lengths`` makes them: None or an int32 device tensor [B*N], planned on the host and copied once)"""
-        if not isinstance(cache, ContextCache):
-            raise TypeError(f'{what}: a ContextCache from prefill_context expected')
-        if cache.forked():
-            raise ValueError(f'{what}: the backward pass has no fork arm: pass cache.materialize() instead of the forked cache')
-        self._refuse_packed(cache, what)
-        B, tshape = cache.B, cache.tshape
-        L = int(np.prod(tshape))
-        self._check_render_shapes(L)
-        cache.check(self)
-        c, dev = self.config, self.device
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
-            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
-        N = query_cameras.shape[1]
-        codes = torch.as_tensor(codes).to(dev)
-        if (codes.dim() != 2 + len(tshape) or codes.shape[0] != B or codes.shape[1] not in (1, N) or tuple(codes.shape[2:]) != tshape
-                or codes.dtype.is_floating_point or codes.dtype == torch.bool):
-            raise ValueError(f'codes int [B={B},N={N} or 1,{",".join(map(str, tshape))}] expected, got {codes.dtype} {tuple(codes.shape)}')
-        return query_cameras, codes, N, self._context_lengths(cache, n_context, N)      # validated on the host before any launch
+        query_cameras, codes, N, _, ctx = self._context_args(what, cache, query_cameras, codes, n_context, one_photo=True, needs='backward')
+        return query_cameras, codes, N, ctx
 
     def _score_grad(self, cache, query_cameras, codes, N, ctx):
         """``score_grad_from_context`` on validated device tensors and prepared context lengths: launches only, nothing here waits for
         the device or copies from the host (tests/test_hip_score_grad.py runs it under torch's synchronisation check)"""
-        c, dev = self.config, self.device
-        B, tshape = cache.B, cache.tshape
-        L = int(np.prod(tshape))
-        d, nE = c.d_model, c.n_embeddings
+        dev, nE, B, tshape, L = self.device, self.config.n_embeddings, cache.B, cache.tshape, cache.L
         M = B * N * L
         if N == 0:
             res = self.score_from_context(cache, query_cameras, codes)
             res['grad_cameras'] = torch.empty((B, 0, 7), dtype=torch.float32, device=dev)
             return res
         target = codes.to(torch.int32).expand(B, N, *tshape).reshape(M).contiguous()
-        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
-        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
+        ids32, add = self._mask_rows(query_cameras, L)
         saved = []
         hf = self._query_rows(cache, ids32, add, N, ctx, save=saved)
         lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
@@ -949,27 +700,10 @@ class MIGT:
         first view).
         ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
         keyword); consecutive views share an attention group, which costs what its longest member costs."""
-        if not isinstance(cache, ContextCache):
-            raise TypeError('sample_from_context: a ContextCache from prefill_context expected')
-        B, tshape = cache.B, cache.tshape
-        L = int(np.prod(tshape))
-        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
-        cache.check(self)
-        c, dev = self.config, self.device
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[2] != 7:
-            raise ValueError(f'query_cameras [B={B},N,7] expected for this cache, got {tuple(query_cameras.shape)}')
-        N = query_cameras.shape[1]
-        S, view0 = int(n_samples), int(view0)
-        if not 1 <= S <= 65535:
-            raise ValueError(f'sample_from_context: 1 <= n_samples <= 65535 expected, got {n_samples}')
-        if not (float(temperature) > 0 and math.isfinite(float(temperature))) or not float(top_p) > 0 or int(top_k) < 0:
-            raise ValueError(f'sample_from_context: temperature > 0 (finite), top_p > 0 and top_k >= 0 expected, got {temperature}, {top_p}, {top_k}')
-        if view0 < 0 or (view0 + N) * L >= 1 << 32:
-            raise ValueError(f'sample_from_context: 0 <= view0 and (view0 + N) * {L} < 2^32 expected, got view0 = {view0}, N = {N}')
-        d, nE = c.d_model, c.n_embeddings
+        S, view0 = self._sampler_args('sample_from_context', n_samples, temperature, top_k, top_p), int(view0)
+        query_cameras, _, N, L, ctx = self._context_args('sample_from_context', cache, query_cameras, n_context=n_context, view0=view0)
+        dev, nE, B, tshape = self.device, self.config.n_embeddings, cache.B, cache.tshape
         M = B * N * L
-        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             res = dict(codes=torch.empty((B, 0, S, *tshape), dtype=torch.int64, device=dev),
                        token_log_prob=torch.empty((B, 0, S, *tshape), dtype=torch.float32, device=dev),
@@ -978,9 +712,7 @@ class MIGT:
             if return_logits:
                 res['logits'] = torch.empty((B, 0, *tshape, nE), dtype=torch.float32, device=dev)
             return res
-        add = self._pose_embed(query_cameras).contiguous().view(B * N, d)
-        ids32 = torch.full((M,), self.mask_token, dtype=torch.int32, device=dev)
-        hf = self._query_rows(cache, ids32, add, N, ctx)
+        hf = self._query_rows(cache, *self._mask_rows(query_cameras, L), N, ctx)
         lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
         self._lm(hf, M, lg)                                                  # migt.py:417
         row_id = ((torch.arange(B, dtype=torch.int64, device=dev) << 32).view(B, 1)
@@ -1009,20 +741,9 @@ class MIGT:
         keyword); consecutive views share an attention group, which costs what its longest member costs."""
         if not self.use_localization:
             raise RuntimeError('localize_from_context needs a model with the localization head')
-        if not isinstance(cache, ContextCache):
-            raise TypeError('localize_from_context: a ContextCache from prefill_context expected')
-        B, tshape = cache.B, cache.tshape
-        L = int(np.prod(tshape))
-        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
-        cache.check(self)
-        c, dev = self.config, self.device
-        codes = torch.as_tensor(codes).to(dev)
-        if codes.dim() != 2 + len(tshape) or codes.shape[0] != B or tuple(codes.shape[2:]) != tshape or codes.dtype.is_floating_point:
-            raise ValueError(f'codes int [B={B},N,{",".join(map(str, tshape))}] expected for this cache, got {codes.dtype} {tuple(codes.shape)}')
-        N = codes.shape[1]
-        d = c.d_model
+        _, codes, N, L, ctx = self._context_args('localize_from_context', cache, codes=codes, n_context=n_context)
+        c, dev, d, B = self.config, self.device, self.config.d_model, cache.B
         M = B * N * L
-        ctx = self._context_lengths(cache, n_context, N)                     # validated on the host before any launch
         if N == 0:
             cams = torch.empty((B, 0, 7), dtype=torch.float32, device=dev)
             if not return_tokens:
@@ -1047,36 +768,6 @@ class MIGT:
         return dict(cameras=cams, pose_prediction=tokens.view(B, N, L, 7), raw=raw.view(B, N, L, 7))
 
     # ------------------------------------------------------------------ a context that grows: appended views, roll-outs along a path
-    def _reserve(self, cache, needed):
-        """room for ``needed`` views per scene: beyond the capacity, new buffers of max(2 capacity, needed) views (render.plan_capacity)"""
-        from .render import plan_capacity
-        if needed > cache.capacity:
-            if cache.forked():                                               # the own room doubles, not the logical capacity (the parent's part is not the fork's)
-                base = int(cache.split.max())
-                self._reallocate(cache, base + plan_capacity(cache.room, needed - base))
-            else:
-                self._reallocate(cache, plan_capacity(cache.capacity, needed))
-
-    def _grown(self, cache, lengths, K):
-        if cache.lengths is None:
-            cache.C += K
-        else:
-            cache.lengths = (lengths + K).astype(np.int32)
-            cache.C = int(cache.lengths.max())
-
-    def _check_growing(self, cache, cameras, what, name):
-        """the refusals ``append_to_context`` and ``rollout_from_context`` share, before any launch -> (cameras on the device, L)"""
-        if not isinstance(cache, ContextCache):
-            raise TypeError(f'{what}: a ContextCache from prefill_context expected')
-        self._refuse_packed(cache, what)
-        L = int(np.prod(cache.tshape))
-        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
-        cache.check(self)
-        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.device)
-        if cameras.dim() != 3 or cameras.shape[0] != cache.B or cameras.shape[2] != 7:
-            raise ValueError(f'{what}: {name} [B={cache.B},.,7] expected for this cache, got {tuple(cameras.shape)}')
-        return cameras, L
-
     def append_to_context(self, cache, codes, cameras):
         """Grow a context in place by K views per scene: ``codes`` int [B,K,t,t], ``cameras`` fp32 [B,K,7] in the context's (relative,
         normalised) frame -> the same ContextCache, K views longer in every scene.  ONE pass over the B*K*L new rows: a context view's own
@@ -1088,94 +779,24 @@ class MIGT:
         K views at once and one by one give the same bits where the dense layers take one kernel for both row counts.  Beyond the capacity the cache moves to
         buffers of max(2 capacity, needed) views, inside the same object.  Foreign caches, the fp8 arm and wrong shapes are refused
         before any launch."""
-        cameras, L = self._check_growing(cache, cameras, 'append_to_context', 'cameras')
-        dev, d, B, tshape = self.device, self.config.d_model, cache.B, cache.tshape
-        codes = torch.as_tensor(codes).to(dev)
-        if (codes.dim() != 2 + len(tshape) or codes.shape[0] != B or tuple(codes.shape[2:]) != tshape or codes.dtype.is_floating_point
-                or codes.dtype == torch.bool or cameras.shape[1] != codes.shape[1]):
-            raise ValueError(f'append_to_context: codes int [B={B},K,{",".join(map(str, tshape))}] and cameras [B,K,7] expected, got {codes.dtype} '
-                             f'{tuple(codes.shape)} and {tuple(cameras.shape)}')
-        K = codes.shape[1]
+        cameras, codes, K, L, _ = self._context_args('append_to_context', cache, cameras, codes, needs='room', lengths=False)
+        dev, d, B = self.device, self.config.d_model, cache.B
         if K == 0:
             return cache
         lengths = cache.filled()
-        self._reserve(cache, int(lengths.max()) + K)
+        cache.reserve(int(lengths.max()) + K)
         pos = torch.from_numpy(lengths).to(dev)
         ctx = torch.from_numpy((lengths.reshape(B, 1) + np.arange(K, dtype=np.int32).reshape(1, K)).astype(np.int32).reshape(-1)).to(dev)
         add = self._pose_embed(cameras).contiguous().view(B * K, d)
         ids32 = codes.reshape(B * K * L).to(torch.int32).contiguous()
         self._query_rows(cache, ids32, add, K, ctx, append_at=pos, tail=None)
-        self._grown(cache, lengths, K)
+        cache.grown(lengths, K)
         return cache
 
     def _replicate(self, cache, S):
-        """a cache of B*S scenes, scene b's S copies at b*S ... b*S+S-1, in buffers of its own"""
-        rep = cache.alias()
-        rep.kv = [kv.view(cache.B, -1).repeat_interleave(S, 0).view(-1, kv.shape[1]) for kv in cache.kv]
-        rep.B = cache.B * S
-        rep.lengths = None if cache.lengths is None else np.repeat(cache.lengths, S).astype(np.int32)
-        if cache.forked():                                                   # the own buffers are copied, the parent's still shared: (b S + s) // (share S) = b // share
-            rep.split = np.repeat(cache.split, S).astype(np.int32)
-            rep.share = cache.share * S
-            rep._split_dev = torch.from_numpy(rep.split).to(self.device)
-            rep._parent = None
-        return rep
+        return cache.replicate(S)
 
     # ------------------------------------------------------------------ forks: children that share a cache's views and own what they add
-    def _fork(self, cache, S, room):
-        from .render import plan_fork
-        if cache.forked():
-            raise ValueError('fork: a fork of a fork is not supported: fork cache.materialize() instead')
-        self._refuse_packed(cache, 'fork')
-        L = int(np.prod(cache.tshape))
-        self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
-        cache.check(self)
-        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) or cache.B * int(S) > 65535:
-            raise ValueError(f'fork: S, an integer >= 1 with B * S <= 65535, expected, got {S}')
-        room = 0 if room is None else room
-        if isinstance(room, bool) or not isinstance(room, (int, np.integer)) or int(room) < 0:
-            raise ValueError(f'fork: room, an integer >= 0, expected, got {room}')
-        S, room = int(S), int(room)
-        split, _ = plan_fork(cache.filled(), S)
-        d = self.config.d_model
-        child = cache.alias()
-        child.parent_kv = list(cache.kv)
-        child.parent_capacity = cache.capacity
-        child.kv = [torch.empty((cache.B * S * room * L, 3 * d), dtype=kv.dtype, device=self.device) for kv in cache.kv]
-        child.B = cache.B * S
-        child.split, child.share, child.room = split, S, room
-        child.lengths = split.copy()
-        child.C = int(split.max()) if split.size else 0
-        child.capacity = child.C + room
-        child._split_dev = torch.from_numpy(split).to(self.device)
-        import weakref
-        child._parent = weakref.ref(cache)
-        return child
-
-    def _materialize(self, cache):
-        cache.check(self)
-        self._refuse_packed(cache, 'materialize')
-        d, L, dev = self.config.d_model, int(np.prod(cache.tshape)), self.device
-        B = cache.B
-        out = cache.alias()
-        if not cache.forked():
-            out.kv = [kv.clone() for kv in cache.kv]
-            return out
-        S, Bp, Cp, room = cache.share, cache.B // cache.share, cache.parent_capacity, cache.room
-        cap = cache.capacity                                                 # split.max() + room: every logical view has its place
-        pos0 = torch.zeros(Bp, dtype=torch.int32, device=dev)
-        kvs = []
-        for pkv, own in zip(cache.parent_kv, cache.kv):
-            dst = torch.empty((B * cap * L, 3 * d), dtype=own.dtype, device=dev)
-            for s in range(S):                                               # the parent's views to child s of every scene (views beyond cap are skipped)
-                ops.kv_append(pkv, dst[s * cap * L:], Bp, Cp, L, d, 3 * d, 3 * d, S * cap * L * 3 * d, cap, pos0)
-            if room:                                                         # the own views behind each scene's split, over whatever the parent held there
-                ops.kv_append(own, dst, B, room, L, d, 3 * d, 3 * d, cap * L * 3 * d, cap, cache._split_dev)
-            kvs.append(dst)
-        out.kv = kvs
-        out.parent_kv = out.parent_capacity = out.split = out.share = out.room = out._parent = out._split_dev = None
-        return out
-
     def adopt_from_fork(self, parent, child, which, score=None):
         """Keep one child's trajectory: the own views of child ``which[b]`` of every scene b are appended to ``parent`` — one
         ``ops.kv_append`` per layer on a gathered source, no row is run again — which then holds what ``append_to_context`` of those views
@@ -1187,8 +808,8 @@ class MIGT:
         from .render import choose_best, plan_fork_lengths
         if not isinstance(parent, ContextCache) or not isinstance(child, ContextCache):
             raise TypeError('adopt_from_fork: two ContextCaches expected')
-        self._refuse_packed(parent, 'adopt_from_fork')
-        self._refuse_packed(child, 'adopt_from_fork')
+        parent.refuse_packed('adopt_from_fork')
+        child.refuse_packed('adopt_from_fork')
         if not child.forked() or parent.forked():
             raise ValueError('adopt_from_fork: a plain parent cache and a cache forked from it expected')
         if child._parent is None or child._parent() is not parent:
@@ -1224,15 +845,13 @@ class MIGT:
         which = which.astype(np.int64)
         if K == 0:
             return which
-        d, L, dev = self.config.d_model, int(np.prod(parent.tshape)), self.device
-        self._reserve(parent, int(lengths.max()) + K)
-        cap = parent.capacity
+        d, L, dev = self.config.d_model, parent.L, self.device
+        parent.reserve(int(lengths.max()) + K)
         pos = torch.from_numpy(lengths).to(dev)
         idx = torch.from_numpy(np.arange(B, dtype=np.int64) * S + which).to(dev)
         for i, own_kv in enumerate(child.kv):
-            src = own_kv.view(B * S, child.room * L, 3 * d)[idx, :K * L].reshape(B * K * L, 3 * d)
-            ops.kv_append(src, parent.kv[i], B, K, L, d, 3 * d, 3 * d, cap * L * 3 * d, cap, pos)
-        self._grown(parent, lengths, K)
+            parent.append(i, own_kv.view(B * S, child.room * L, 3 * d)[idx, :K * L].reshape(B * K * L, 3 * d), K, pos)
+        parent.grown(lengths, K)
         return which
 
     def rollout_from_context(self, cache, path_cameras, n_samples: int = 1, temperature: float = 1.0, top_k: int = 1, top_p: float = 1.0,
@@ -1256,21 +875,15 @@ class MIGT:
         ``fork=True`` (with S > 1; opt-in): the S trajectories run on ``cache.fork(S, room=T)`` instead of a replicated cache — the
         photographs' keys are read where they lie, only the T generated views per trajectory get buffers — with the same bits, the same
         noise keys and the fork as the returned ``cache`` (``adopt_from_fork`` keeps one trajectory in ``cache``)."""
-        path_cameras, L = self._check_growing(cache, path_cameras, 'rollout_from_context', 'path_cameras')
+        S = self._sampler_args('rollout_from_context', n_samples, temperature, top_k, top_p)
+        path_cameras, _, T, L, _ = self._context_args('rollout_from_context', cache, path_cameras, needs='room', lengths=False)
         c, dev = self.config, self.device
-        d, nE, tshape = c.d_model, c.n_embeddings, cache.tshape
-        B, T, S = cache.B, path_cameras.shape[1], int(n_samples)
-        if not 1 <= S <= 65535 or S != n_samples:
-            raise ValueError(f'rollout_from_context: 1 <= n_samples <= 65535 expected, got {n_samples}')
-        if not (float(temperature) > 0 and math.isfinite(float(temperature))) or not float(top_p) > 0 or int(top_k) < 0:
-            raise ValueError(f'rollout_from_context: temperature > 0 (finite), top_p > 0 and top_k >= 0 expected, got {temperature}, {top_p}, {top_k}')
+        d, nE, tshape, B = c.d_model, c.n_embeddings, cache.tshape, cache.B
         if T * L >= 1 << 32 or B * S >= 1 << 31:
             raise ValueError(f'rollout_from_context: T * {L} < 2^32 and B * n_samples < 2^31 expected, got T = {T}, B = {B}, n_samples = {S}')
         from .render import plan_rollout_lengths, plan_replication, rollout_row_ids
-        if fork and S > 1 and cache.forked():
-            raise ValueError('rollout_from_context: fork=True on a forked cache would be a fork of a fork: pass cache.materialize()')
-        if S > 1:
-            cache = self._fork(cache, S, T) if fork else self._replicate(cache, S)
+        if S > 1:                                                            # (fork=True on a fork: refused there, a fork of a fork)
+            cache = cache.fork(S, T) if fork else cache.replicate(S)
             path_cameras = path_cameras[torch.from_numpy(plan_replication(B, S)).to(dev)]
         Bs = B * S
         M = Bs * L
@@ -1278,7 +891,7 @@ class MIGT:
         gen, pair = plan_rollout_lengths(lengths, T)                         # [T,Bs] and [T,Bs,2], host
         codes, tlps, lls, lgs = [], [], [], []
         if T:
-            self._reserve(cache, int(lengths.max()) + T)
+            cache.reserve(int(lengths.max()) + T)
             gen_dev = torch.from_numpy(gen).to(dev)
             pair_dev = torch.from_numpy(pair.reshape(T, Bs * 2)).to(dev)
             pe = self._pose_embed(path_cameras)                              # [Bs,T,d]
@@ -1303,7 +916,7 @@ class MIGT:
                 if return_logits:
                     lgs.append(lg.view(Bs, L, nE))
             self._query_rows(cache, prev, pe[:, T - 1].contiguous(), 1, gen_dev[T - 1], append_at=gen_dev[T - 1], tail=None)
-            self._grown(cache, lengths, T)
+            cache.grown(lengths, T)
         stack = lambda xs, dt, *tail: (torch.stack(xs, 1) if xs else torch.empty((Bs, 0, *tail), dtype=dt, device=dev))
         res = dict(codes=stack(codes, torch.int64, L).view(B, S, T, *tshape), token_log_prob=stack(tlps, torch.float32, L).view(B, S, T, *tshape),
                    log_likelihood=stack(lls, torch.float32).view(B, S, T), cache=cache)

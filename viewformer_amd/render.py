@@ -319,27 +319,29 @@ class ViewRenderer:
         them as e4m3 bytes with a power-of-two scale per (scene, view, head) — about 1/3 of the bf16 bytes, the answers of the bf16 arm
         on the dequantised cache.  ``render``, ``sample``, ``score``, ``localize`` and ``sweep`` go on working; ``append``, ``rollout``,
         ``fork``, ``score_gradient`` and ``refine`` refuse until ``unpack()``."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.pack: set_context() first')
+        self._context('pack')
         self.cache = self.cache.pack(dtype)
         return self
 
     def unpack(self):
         """Undo ``pack``: a plain cache again (the K/V-only form bit for bit, the e4m3 form dequantised; the Q third zeros), in place."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.unpack: set_context() first')
+        self._context('unpack')
         self.cache = self.cache.unpack()
         return self
 
     def context_bytes(self):
         """the bytes of the context cache's own tensors, from their shapes"""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.context_bytes: set_context() first')
+        self._context('context_bytes')
         return self.cache.nbytes()
 
+    def _context(self, what):
+        """the context cache, for ``what``"""
+        if self.cache is None:
+            raise RuntimeError(f'ViewRenderer.{what}: set_context() first')
+        return self.cache
+
     def _refuse_packed(self, what):
-        if self.cache.packed is not None:
-            raise ValueError(f'ViewRenderer.{what}: the context is packed ({self.cache.packed!r}) and read-only: unpack() first')
+        self.cache.refuse_packed(f'ViewRenderer.{what}')
 
     def _own_lengths(self, cache):
         """before the context grows: a ragged batch's valid views (``set_context(n_context=...)``) become the cache's own lengths, so
@@ -367,8 +369,7 @@ class ViewRenderer:
         ``cameras`` [B,K,7] in the caller's world frame (the context's: view 0 stays the frame).  The context grows in place by K views
         per scene in one pass over the new views (``MIGT.append_to_context``): no earlier view is run again.  Every later ``render``,
         ``sample``, ``score``, ``localize`` and ``sweep`` sees the grown context; ``n_context`` and ``context_codes`` follow."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.append: set_context() first')
+        self._context('append')
         self._refuse_packed('append')
         if cameras is None or (images is None) == (codes is None):
             raise ValueError('append: cameras and exactly one of images / codes expected')
@@ -403,8 +404,7 @@ class ViewRenderer:
         adds — with ``transform``, ``context_codes`` and ``n_context`` repeated per child.  Its ``append``, ``rollout(keep=True)``,
         ``render``, ``sample``, ``score`` and ``localize`` work as on any renderer and never touch this one; ``score_gradient`` and
         ``refine`` need ``cache.materialize()``."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.fork: set_context() first')
+        self._context('fork')
         self._refuse_packed('fork')
         if isinstance(S, bool) or int(S) != S or int(S) < 1:
             raise ValueError(f'fork: S, an integer >= 1, expected, got {S}')
@@ -435,8 +435,7 @@ class ViewRenderer:
         after the roll-out ONE trajectory per scene stays in the renderer's own context (``MIGT.adopt_from_fork``; no row is run
         again), ``'best'`` being the one with the largest sum of ``log_likelihood`` over T, ties going to the lowest index;
         ``context_codes`` and ``n_context`` follow as with ``keep=True`` for S = 1, and the result gains ``adopted`` int64 [B]."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.rollout: set_context() first')
+        self._context('rollout')
         self._refuse_packed('rollout')
         if adopt is not None and not (fork and int(n_samples) > 1):
             raise ValueError('rollout: adopt goes with fork=True and n_samples > 1 (keep=True keeps the one trajectory of n_samples = 1)')
@@ -523,8 +522,7 @@ class ViewRenderer:
         ``n_context``: an int, [B] or [B,N] in [0, C] — the number of leading context views each query sees, overriding
         ``set_context``'s per-scene default; sliced per chunk with the views.  4 (bf16) / 2 (f32) consecutive views share an attention
         workgroup, which costs what its longest member costs: keep equal lengths together (``sweep`` does)."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.render: set_context() first')
+        self._context('render')
         tm, cm = self.transformer, self.codebook
         dev = cm.device
         query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
@@ -575,8 +573,7 @@ class ViewRenderer:
         noise is keyed by b, a scene set as the context alone (b = 0) and the same scene at b = 1 of a batch get DIFFERENT draws for one
         seed (same distribution, same kept sets, same ``top_k = 1`` result); only scene 0 of a batch reproduces its stand-alone draws.
         ``n_context``: as ``render``'s."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.sample: set_context() first')
+        self._context('sample')
         tm, cm = self.transformer, self.codebook
         dev = cm.device
         query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
@@ -609,8 +606,7 @@ class ViewRenderer:
         ranking candidate poses.  N is walked in chunks of whole views (``plan_view_chunks``); a view's result does not depend on the
         chunking.  ``self.fused_score`` (None = the model's default route, True / False = the fused head / through the logits) is for A/B runs.
         ``n_context``: as ``render``'s."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.score: set_context() first')
+        self._context('score')
         if (images is None) == (codes is None):
             raise ValueError('score: exactly one of images / codes expected')
         tm, cm = self.transformer, self.codebook
@@ -680,11 +676,8 @@ class ViewRenderer:
         model was trained so, normalised) that the gradient refers to: grad_cameras[b,n] = d log_likelihood[b,n] / d poses[b,n].
         Arguments as ``score``'s; N is walked in chunks of whole views (``plan_view_chunks``), a view's result does not depend on the
         chunking."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.score_gradient: set_context() first')
-        self._refuse_packed('score_gradient')
-        if self.cache.forked():
-            raise ValueError('ViewRenderer.score_gradient: the backward pass has no fork arm: set the cache to cache.materialize() first')
+        self._context('score_gradient')
+        self.cache.refuse_backward('ViewRenderer.score_gradient')
         query_cameras = self._world_cameras('score_gradient', query_cameras)
         B, N = self.cache.B, query_cameras.shape[1]
         codes = self._photo_codes('score_gradient', images, codes, N)
@@ -708,11 +701,8 @@ class ViewRenderer:
         ``codes`` as ``score``'s -> dict(generated_cameras fp32 [B,N,7] in the world frame, through ``from_relative_cameras`` as
         ``localize``; cameras [B,N,7] in the model's frame; log_likelihood, initial_log_likelihood fp32 [B,N]; accepted int32 [B,N]; with
         ``return_trace`` trace fp32 [steps+1,B,N]).  N is walked in chunks of whole views; views are refined independently of each other."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.refine: set_context() first')
-        self._refuse_packed('refine')
-        if self.cache.forked():
-            raise ValueError('ViewRenderer.refine: the backward pass has no fork arm: set the cache to cache.materialize() first')
+        self._context('refine')
+        self.cache.refuse_backward('ViewRenderer.refine')
         B = self.cache.B
         if cameras0 is not None:
             cameras0 = self._world_cameras('refine', cameras0)
@@ -741,8 +731,7 @@ class ViewRenderer:
         ``SceneBank.gather``) -> dict(generated_cameras fp32 [B,N,7]) in the caller's world frame (the context cameras'); with
         ``return_tokens`` also codes int32 [B,N,t,t], pose_prediction [B,N,L,7] (the per-token poses in the context's frame) and raw
         [B,N,L,7].  N is walked in chunks of whole views (``plan_view_chunks``).  ``n_context``: as ``render``'s."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.localize: set_context() first')
+        self._context('localize')
         if (images is None) == (codes is None):
             raise ValueError('localize: exactly one of images / codes expected')
         tm, cm = self.transformer, self.codebook
@@ -785,8 +774,7 @@ class ViewRenderer:
         with ``return_codes`` also generated_codes int64 [B,N,K,t,t] and logits fp32 [B,N,K,t,t,n_embeddings].  ONE ``render`` over
         K N views laid out size-major (``sweep_layout``), from the one prefill: no context is encoded or prefilled per size.  After
         ``set_context(n_context=...)`` a size above a scene's number of valid views is that number (its padding is never read)."""
-        if self.cache is None:
-            raise RuntimeError('ViewRenderer.sweep: set_context() first')
+        self._context('sweep')
         B, C = self.cache.B, self.cache.C
         query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(self.codebook.device)
         if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
