@@ -367,6 +367,17 @@ int vf_attn_prefix_bwd_f32(const void* q, const void* k, const void* v, const vo
  * B, K, L, d or capacity == 0: no-op, VF_OK. */
 int vf_kv_append(const void* qkv, void* cache, int elem_bytes, int B, int K, int L, int d, int ld_src, int ld_dst, int64_t cache_stride,
                  int capacity, const int32_t* pos, void* stream);
+/* vf_kv_append for a cache that holds no Q third (csrc/kv_append.hip, the same copy loop; a growing K/V-only cache): qkv, pos, capacity and
+ * the skipping rule as there; for scene b and new view j the K third (columns [2d, 3d)) of the view's L rows goes to columns [0, d) of rows
+ * (pos[b] + j) L ... of scene b of `k` (leading dimension ld_k, scenes k_stride elements apart), the V third (columns [0, d)) to the same
+ * rows of `v` (ld_v, v_stride).  One launch; 16-byte chunks per thread; the copy is bit-exact.  Footprint: reads the two thirds of the
+ * B*K*L rows and pos; writes exactly the d logical columns of the rows named above in k and in v — every other row, the row gaps and every
+ * other scene keep their bits.  NULL or not 16-byte aligned qkv / k / v, NULL pos, elem_bytes not in {2, 4}, a negative size or stride,
+ * ld_src < 3 d, ld_k or ld_v < d, d / ld_* / *_stride times elem_bytes not a multiple of 16, or (B > 1) a scene stride below one scene's
+ * extent: VF_ERR_BAD_ARG; B K or the 16-byte chunks of one view above 2^31 - 1: VF_ERR_UNSUPPORTED; both before any launch.  B, K, L, d
+ * or capacity == 0: no-op, VF_OK. */
+int vf_kv_append_split(const void* qkv, void* k, void* v, int elem_bytes, int B, int K, int L, int d, int ld_src, int ld_k, int ld_v,
+                       int64_t k_stride, int64_t v_stride, int capacity, const int32_t* pos, void* stream);
 /* Pack the K and V thirds of a context cache to OCP e4m3 bytes with one power-of-two fp32 scale per (scene, view, head) tile of
  * 64 tokens x 64 features (csrc/kv_pack.hip; ContextCache.pack('e4m3')).  cache: a layer's buffer as vf_kv_append takes it — rows
  * [C*L][ld_src] per scene, thirds (V, Q, K) of d = 64 H columns each, scenes cache_stride elements apart, elem_bytes 2 (bf16) or 4 (fp32).
@@ -385,6 +396,20 @@ int vf_kv_append(const void* qkv, void* cache, int elem_bytes, int B, int K, int
 int vf_kv_pack_e4m3(const void* cache, int elem_bytes, void* kq, void* vq, float* kscale, float* vscale, int B, int C, int H, int L,
                     int ld_src, int64_t cache_stride, int64_t q_view_stride, int64_t q_scene_stride, int64_t s_view_stride,
                     int64_t s_scene_stride, const int32_t* lengths, void* stream);
+/* The quantising form of vf_kv_append (csrc/kv_append_e4m3.hip; a growing e4m3 cache): qkv = the fused c_attn output of K new views per
+ * scene, rows [B*K*L][ld_src], thirds (V, Q, K) of d = 64 H columns each, elem_bytes 2 (bf16) or 4 (fp32); pos: DEVICE pointer to [B] int32.
+ * New view j of scene b goes to slot pos[b] + j of the packed buffers: its K tiles to kq, its V tiles (transposed) to vq, their scales to
+ * kscale / vscale, all addressed exactly as vf_kv_pack_e4m3 addresses view c = slot.  A slot outside [0, capacity) is skipped: nothing of
+ * that view is read, nothing written (vf_kv_append's clamp).  Scale rule, saturation, NaN handling and rounding are vf_kv_pack_e4m3's, by
+ * the same device routine (csrc/kv_tile_e4m3.h): equal tile values give equal bytes and equal scales in the two entries.  One workgroup per
+ * (scene, new view, head, K | V) tile; a tile leaves as 256 16-byte vector stores.  Footprint: reads the V and K thirds of the B*K*L rows
+ * (never the Q third) and pos; writes exactly the tiles and scales of the slots named above — every other slot, the gaps between views
+ * and scenes and everything around the buffers keep their bits.  Checks as vf_kv_pack_e4m3's (no cache_stride: the source is contiguous in
+ * views), and NULL pos, a negative capacity, or (B > 1) a scene stride below `capacity` views' extent: VF_ERR_BAD_ARG; L != 64,
+ * B K > 2^31 - 1, H > 65535: VF_ERR_UNSUPPORTED; all before any launch.  B, K or capacity == 0: no-op, VF_OK. */
+int vf_kv_append_e4m3(const void* qkv, int elem_bytes, void* kq, void* vq, float* kscale, float* vscale, int B, int K, int H, int L,
+                      int ld_src, int64_t q_view_stride, int64_t q_scene_stride, int64_t s_view_stride, int64_t s_scene_stride,
+                      int capacity, const int32_t* pos, void* stream);
 /* vf_attn_prefix_var_bf16 over a cache packed by vf_kv_pack_e4m3 (the kernel's Q8 instantiation): kq / vq / kscale / vscale and the four
  * strides as there, C = the views of room per scene in the packed buffers; q / k / v (bf16 or fp32 by in_bf16), out, ld*, ctx_len (a length
  * per query view, clamped to [0, C]) as the VAR entry's.  A packed tile is fetched as one contiguous 4 KiB block, dequantised (e4m3 * scale,

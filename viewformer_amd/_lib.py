@@ -108,7 +108,9 @@ EXPORTS = {
     'vf_attn_prefix_fork_f32eq': (c_int, [P, P, P, P, P, P] + [c_int] * 11 + [c_int64, c_int, P, P, P, c_int, c_int, c_int, c_int64, P, c_int, P]),
     'vf_attn_prefix_bwd_f32': (c_int, [P, P, P, P, P, c_int, P, P] + [c_int] * 11 + [c_int64, c_int, c_int, P, P]),
     'vf_kv_append': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, P, P]),
+    'vf_kv_append_split': (c_int, [P, P, P] + [c_int] * 8 + [c_int64, c_int64, c_int, P, P]),
     'vf_kv_pack_e4m3': (c_int, [P, c_int, P, P, P, P] + [c_int] * 5 + [c_int64] * 5 + [P, P]),
+    'vf_kv_append_e4m3': (c_int, [P, c_int, P, P, P, P] + [c_int] * 5 + [c_int64] * 4 + [c_int, P, P]),
     'vf_attn_prefix_q8_bf16': (c_int, [P] * 7 + [c_int, P, c_int] + [c_int] * 9 + [c_int64] * 4 + [c_int, P, P]),
     'vf_attn_blockcausal_lse_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                             c_float, c_int, c_int, c_float, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]),

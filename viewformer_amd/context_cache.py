@@ -20,7 +20,8 @@ class ContextCache:
     arm and device that made it.  ``capacity`` >= C views of room per scene (``prefill_context(capacity=...)``, grown by
     ``append_to_context``); ``C`` = the number of filled views, the maximum over scenes; ``lengths``: the filled views per scene, host
     int32 [B], or None for "all C" — tight, slack and ragged caches are this one form: lengths are data.  The other forms are its
-    subclasses ``ForkedContextCache`` (``fork``), ``PackedKVCache`` and ``PackedE4M3Cache`` (``pack``)."""
+    subclasses ``ForkedContextCache`` (``fork``), ``PackedKVCache`` and ``PackedE4M3Cache`` (``pack``), and the packed forms with room
+    ``GrowingKVCache`` and ``GrowingE4M3Cache`` (``pack(room=...)``, ``prefill_context(pack=...)``)."""
     packed = None                     # None, 'kv' or 'e4m3'
     parent_kv = parent_capacity = split = share = room = _parent = _split_dev = None      # a fork's
 
@@ -77,6 +78,9 @@ class ContextCache:
 
     def refuse_packed(self, what):
         """``what`` grows, forks, copies or differentiates: a packed form refuses it"""
+
+    def refuse_growth(self, what):
+        """``what`` appends views: a packed form without room refuses it"""
 
     def refuse_backward(self, what):
         """``what`` needs ``attend_backward``: only the plain form has it"""
@@ -178,7 +182,7 @@ class ContextCache:
         them, copied bit for bit by ``ops.kv_append`` (every result on it has the fork's bits).  On a plain cache: a copy."""
         return ContextCache(self._model('materialize'), [kv.clone() for kv in self.kv], self.B, self.C, self.tshape, self.capacity, self.lengths)
 
-    def pack(self, dtype=None):
+    def pack(self, dtype=None, room=None):
         """A packed, READ-ONLY cache of the same scenes in buffers of its own (this cache is left untouched), tight (capacity =
         the longest scene), lengths kept.  ``dtype=None``: the K and V thirds only, in the cache's dtype — 2/3 of the bytes, both arms,
         every result ``torch.equal`` to this cache's.  ``dtype='e4m3'`` (``precision='bf16'`` models only): OCP e4m3 bytes with one
@@ -186,16 +190,23 @@ class ContextCache:
         result has the bits of the bf16 arm on ``unpack()``'s dequantised cache, and what is lost is the quantisation alone.
         ``generate`` / ``sample`` / ``score`` / ``localize_from_context`` take a packed cache as any cache; whatever grows a cache, forks
         it or differentiates through it refuses it: ``unpack()`` first.  A fork or a packed cache is refused: ``materialize()`` /
-        ``unpack()`` first."""
+        ``unpack()`` first.
+        ``room=R`` (an integer >= 0; opt-in): the GROWING packed form of the same ``dtype`` instead (``GrowingKVCache`` /
+        ``GrowingE4M3Cache``) — ``capacity`` = C + R views per scene, the slack zero bytes (scales 1), and
+        ``append_to_context`` / ``rollout_from_context`` take it; forks and gradients still need ``unpack()``."""
         m = self._model('pack')
         if dtype is not None and dtype != 'e4m3':
             raise ValueError(f"pack: dtype None (the K and V thirds as they are) or 'e4m3' expected, got {dtype!r}")
+        if room is not None and (isinstance(room, bool) or not isinstance(room, (int, np.integer)) or int(room) < 0):
+            raise ValueError(f'pack: room None (the tight, read-only pack) or an integer >= 0 expected, got {room!r}')
         if dtype == 'e4m3' and m.precision != 'bf16':
             raise ValueError(f"pack: dtype='e4m3' is for precision='bf16' models; the {m.precision!r} arm exists for exactness: "
                              'pack(dtype=None) keeps its bits')
         m._check_render_shapes(self.L)
         d, H, L, B, C, cap, dev = self.d, self.H, self.L, self.B, self.C, self.capacity, self.device
         lengths = self.filled() if self.ragged() else None                       # the length route whenever the source takes it
+        if room is not None:
+            return self._pack_with_room(m, dtype, C + int(room), lengths)
         if dtype is None:
             kvs = [tuple(kv.view(B, cap * L, 3 * d)[:, :C * L, a:a + d].contiguous().view(B * C * L, d) for a in (2 * d, 0)) for kv in self.kv]
             return PackedKVCache(m, kvs, B, C, self.tshape, lengths)
@@ -210,6 +221,27 @@ class ContextCache:
                 ops.kv_pack_e4m3(kv, kq, vq, ks, vs, B, C, H, L, 3 * d, cap * L * 3 * d, filled)
             kvs.append((kq, vq, ks, vs))
         return PackedE4M3Cache(m, kvs, B, C, self.tshape, lengths)
+
+    def _pack_with_room(self, m, dtype, capn, lengths):
+        """``pack(dtype, room=capn - C)``: this cache's C leading views into fresh buffers of ``capn`` views per scene"""
+        d, H, L, B, C, cap, dev = self.d, self.H, self.L, self.B, self.C, self.capacity, self.device
+        if dtype is None:
+            kvs = []
+            for kv in self.kv:
+                k, v = GrowingKVCache.buffers(B, capn, L, d, kv.dtype, dev)
+                src = kv.view(B, cap * L, 3 * d)[:, :C * L]
+                k.view(B, capn * L, d)[:, :C * L] = src[:, :, 2 * d:]
+                v.view(B, capn * L, d)[:, :C * L] = src[:, :, :d]
+                kvs.append((k, v))
+            return GrowingKVCache(m, kvs, B, C, self.tshape, capn, lengths)
+        filled = torch.from_numpy(self.filled()).to(dev)
+        kvs = []
+        for kv in self.kv:
+            t = GrowingE4M3Cache.buffers(B, capn, H, dev)
+            if B and C:
+                ops.kv_pack_e4m3(kv, *t, B, C, H, L, 3 * d, cap * L * 3 * d, filled, q_scene_stride=capn * H * 4096, s_scene_stride=capn * H)
+            kvs.append(t)
+        return GrowingE4M3Cache(m, kvs, B, C, self.tshape, capn, lengths)
 
     def unpack(self):
         """A plain cache (thirds V, Q, K) of a packed one, in buffers of its own: the K and V thirds bit for bit (K/V-only form)
@@ -292,7 +324,7 @@ class ForkedContextCache(ContextCache):
         self._model('fork')
         raise ValueError('fork: a fork of a fork is not supported: fork cache.materialize() instead')
 
-    def pack(self, dtype=None):
+    def pack(self, dtype=None, room=None):
         self._model('pack')
         raise ValueError('pack: a forked cache reads two segments: pack cache.materialize() instead')
 
@@ -324,7 +356,7 @@ class PackedKVCache(ContextCache):
     def refuse_packed(self, what):
         raise ValueError(f'{what}: a packed cache is read-only (it holds no Q third and has no room): pass cache.unpack() instead')
 
-    refuse_backward = refuse_packed
+    refuse_backward = refuse_growth = refuse_packed
 
     def _refuse(self, what):
         self._model(what)
@@ -354,12 +386,12 @@ class PackedKVCache(ContextCache):
     def materialize(self):
         self._refuse('materialize')
 
-    def pack(self, dtype=None):
+    def pack(self, dtype=None, room=None):
         self._model('pack')
         raise ValueError(f'pack: this cache is packed already ({self.packed!r}): pack cache.unpack() instead')
 
     def _thirds(self, dt):
-        """(K, V) of every layer, each [B*C*L, d] in the plain form's dtype ``dt``"""
+        """(K, V) of every layer, each [B*capacity*L, d] in the plain form's dtype ``dt``"""
         return self.kv
 
     def unpack(self):
@@ -367,7 +399,7 @@ class PackedKVCache(ContextCache):
         dt = torch.bfloat16 if self.qkv16 else torch.float32
         kvs = []
         for k, v in self._thirds(dt):
-            kv = torch.zeros((self.B * self.C * self.L, 3 * self.d), dtype=dt, device=self.device)
+            kv = torch.zeros((self.B * self.capacity * self.L, 3 * self.d), dtype=dt, device=self.device)
             kv[:, 2 * self.d:], kv[:, :self.d] = k, v
             kvs.append(kv)
         return ContextCache(m, kvs, self.B, self.C, self.tshape, self.capacity, self.lengths)
@@ -394,9 +426,120 @@ class PackedE4M3Cache(PackedKVCache):
 
     def _thirds(self, dt):
         """byte -> value through the 256 e4m3 numbers (exact), times the tile's scale"""
-        n = self.B * self.C
+        n = self.B * self.capacity
         lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(self.device)
         for kq, vq, ks, vs in self.kv:
             k = lut[kq.long()] * ks.view(n, self.H, 1, 1)                    # [B*C, H, key, feature]
             v = lut[vq.long()] * vs.view(n, self.H, 1, 1)                    # [B*C, H, feature, key]
             yield k.permute(0, 2, 1, 3).reshape(n * self.L, self.d).to(dt), v.permute(0, 3, 1, 2).reshape(n * self.L, self.d).to(dt)
+
+
+class _Growing:
+    """What the two packed forms WITH ROOM share: ``capacity`` >= ``C`` views of room per scene in every tensor,
+    lengths as data (the plain form's ``filled`` / ``ragged`` / ``grown``), ``append`` as ONE launch of the form's own append kernel at
+    each scene's own length, the parent form's ``attend`` with ``capacity`` as the attention's C, and ``reserve`` / ``reallocate`` by
+    ``render.plan_capacity`` with one strided device copy per tensor.  Forks, ``materialize``, ``pack`` and the backward pass refuse as
+    on every packed cache and name ``unpack()``, which gives a plain cache of the same capacity and lengths."""
+
+    def refuse_packed(self, what):
+        raise ValueError(f'{what}: a packed cache holds no Q third (it grows, but it cannot be forked, copied to a plain one or '
+                         'differentiated through): pass cache.unpack() instead')
+
+    refuse_backward = refuse_packed
+
+    def refuse_growth(self, what):
+        """(``append_to_context`` and ``rollout_from_context`` are what this form is for)"""
+
+    def plan_pass(self, n_context, append_at=None, save=None):
+        if save is not None:
+            self.refuse_backward('_query_rows')
+        return append_at
+
+    reserve = ContextCache.reserve
+
+    def reallocate(self, capacity):
+        """new buffers of ``capacity`` views per scene inside the same cache: every tensor's ``self.capacity`` views of every scene
+        moved by one strided copy, bit for bit (bytes and scales included); the new slack as ``buffers`` leaves it"""
+        B, old = self.B, self.capacity
+        for i, ts in enumerate(self.kv):
+            new = self._buffers(capacity, ts[0].dtype)
+            for dst, src in zip(new, ts):
+                dst.view(B, capacity, -1)[:, :old] = src.view(B, old, -1)
+            self.kv[i] = new
+        self.capacity = capacity
+
+    def replicate(self, S):
+        kv = [tuple(t.view(self.B, -1).repeat_interleave(S, 0).view(-1, *t.shape[1:]) for t in ts) for ts in self.kv]
+        return type(self)(self._model('replicate'), kv, self.B * S, self.C, self.tshape, self.capacity,
+                          None if self.lengths is None else np.repeat(self.lengths, S))
+
+
+class GrowingKVCache(_Growing, PackedKVCache):
+    """The K/V-only pack WITH ROOM: ``kv[i]`` = (K, V), two contiguous [B*capacity*L, d_model] tensors in the cache's
+    dtype, scenes capacity*L*d_model apart — the plain cache's own K and V values, appended by ``ops.kv_append_split`` and walked by the
+    plain prefix attention with ld d: every answer ``torch.equal`` to the answer of a plain cache grown the same way."""
+
+    def __init__(self, model, kv, B, C, tshape, capacity, lengths=None):
+        ContextCache.__init__(self, model, kv, B, C, tshape, capacity, lengths)
+
+    @staticmethod
+    def buffers(B, capacity, L, d, dtype, device):
+        """one layer's (K, V) with room for ``capacity`` views per scene, zeros"""
+        return tuple(torch.zeros((B * capacity * L, d), dtype=dtype, device=device) for _ in range(2))
+
+    def _buffers(self, capacity, dtype):
+        return self.buffers(self.B, capacity, self.L, self.d, dtype, self.device)
+
+    def append(self, i, qkv, N, at):
+        d, L, cap = self.d, self.L, self.capacity
+        k, v = self.kv[i]
+        ops.kv_append_split(qkv, k, v, self.B, N, L, d, 3 * d, d, d, cap * L * d, cap * L * d, cap, at)
+
+
+class GrowingE4M3Cache(_Growing, PackedE4M3Cache):
+    """The e4m3 pack WITH ROOM (bf16 arm): ``kv[i]`` = (kq, vq uint8 [B*capacity, H, 64, 64], kscale, vscale fp32
+    [B*capacity, H]).  A new view brings its own tiles and scales (``ops.kv_append_e4m3``, the pack kernel's tile routine) and touches
+    nothing that is stored; ``ops.attn_prefix_q8`` reads the buffers with ``capacity`` as its C."""
+
+    def __init__(self, model, kv, B, C, tshape, capacity, lengths=None):
+        ContextCache.__init__(self, model, kv, B, C, tshape, capacity, lengths)
+
+    @staticmethod
+    def buffers(B, capacity, H, device):
+        """one layer's (kq, vq, kscale, vscale) with room for ``capacity`` views per scene: zero bytes, scales 1"""
+        return (torch.zeros((B * capacity, H, 64, 64), dtype=torch.uint8, device=device),
+                torch.zeros((B * capacity, H, 64, 64), dtype=torch.uint8, device=device),
+                torch.ones((B * capacity, H), dtype=torch.float32, device=device),
+                torch.ones((B * capacity, H), dtype=torch.float32, device=device))
+
+    def _buffers(self, capacity, dtype):
+        return self.buffers(self.B, capacity, self.H, self.device)
+
+    def plan_pass(self, n_context, append_at=None, save=None):
+        at = _Growing.plan_pass(self, n_context, append_at, save)
+        if n_context is None or self.arm[0] != 'bf16':
+            raise ValueError('_query_rows: an e4m3 cache takes the length route of the bf16 arm')
+        return at
+
+    def append(self, i, qkv, N, at):
+        ops.kv_append_e4m3(qkv, *self.kv[i], self.B, N, self.H, self.L, 3 * self.d, self.capacity, at)
+
+
+class PrefillSink:
+    """What ``MIGT._blocks`` takes as ``kv_sink`` when ``prefill_context(pack=...)`` fills a growing packed cache directly: ``_blocks``
+    hands over each layer's fused c_attn buffer BEFORE it launches the GEMM that fills it, so the buffer of layer i is appended to the
+    cache (at position 0, one launch) when layer i + 1's arrives — stream order puts that behind the GEMM — or at ``close()``, and is
+    dropped then: the plain cache of all layers never exists."""
+
+    def __init__(self, cache, C):
+        self.cache, self.C, self.layer, self.pending = cache, C, 0, None
+        self.pos0 = torch.zeros(cache.B, dtype=torch.int32, device=cache.device)
+
+    def append(self, qkv):
+        self.close()
+        self.pending = qkv
+
+    def close(self):
+        if self.pending is not None:
+            self.cache.append(self.layer, self.pending, self.C, self.pos0)
+            self.layer, self.pending = self.layer + 1, None

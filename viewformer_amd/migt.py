@@ -24,7 +24,7 @@ import torch
 from . import ops
 from . import geometry
 from .config import MIGTConfig
-from .context_cache import ContextCache                # noqa: F401  (tests and tools import it from here)
+from .context_cache import ContextCache, GrowingKVCache, GrowingE4M3Cache, PrefillSink      # noqa: F401  (tests and tools import ContextCache from here)
 
 
 class _Dense:
@@ -306,7 +306,7 @@ class MIGT:
             raise ops._lib.VfError(f'prefix-cache attention supports head dim 64 and 64-token views only (got head dim '
                                    f'{c.d_model // c.n_head}, {L} tokens)')
 
-    def prefill_context(self, codes, cameras, capacity=None):
+    def prefill_context(self, codes, cameras, capacity=None, pack=None):
         """Run the C context views once and keep every layer's keys and values: ``codes`` int [B,C,t,t], ``cameras`` fp32 [B,C,7]
         (relative + normalised) -> ContextCache for ``generate_from_context``.  Block-causal attention never shows a context view the
         target, ``wpe`` indexes the token inside a view and the poses are relative to view 0, so the context's hidden states — and each
@@ -314,7 +314,16 @@ class MIGT:
         third is not read again): no copy, dtype as the arm's ``qkv``.
         ``capacity`` >= C: room for that many views per scene and layer ([B*capacity*L, 3d], scenes capacity*L*3d apart), the prefilled
         views put there by ``ops.kv_append`` at position 0 — for ``append_to_context`` / ``rollout_from_context``, which otherwise
-        reallocate at their first call.  Without it: the buffers and launches above, nothing else."""
+        reallocate at their first call.  Without it: the buffers and launches above, nothing else.
+        ``pack``: None, or ``'kv'`` / ``'e4m3'`` (``'e4m3'``: ``precision='bf16'`` models only): fill a GROWING packed cache of that form
+        directly — each layer's fused c_attn output goes to the packed buffers by that form's one append launch at
+        position 0 and is dropped, so the plain cache of all layers never exists — with every tensor equal, bit for bit, to
+        ``prefill_context(codes, cameras).pack(dtype, room=capacity - C)``."""
+        if pack not in (None, 'kv', 'e4m3'):
+            raise ValueError(f"prefill_context: pack None, 'kv' or 'e4m3' expected, got {pack!r}")
+        if pack == 'e4m3' and self.precision != 'bf16':
+            raise ValueError(f"prefill_context: pack='e4m3' is for precision='bf16' models; the {self.precision!r} arm exists for "
+                             "exactness: pack='kv' keeps its bits")
         codes = torch.as_tensor(codes).to(self.device)
         cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.device)
         if codes.dim() < 3 or cameras.shape[:2] != codes.shape[:2] or cameras.shape[-1] != 7 or codes.shape[1] < 1:
@@ -325,6 +334,19 @@ class MIGT:
         tshape = tuple(codes.shape[2:])
         L = int(np.prod(tshape))
         self._check_render_shapes(L)
+        if pack is not None:
+            c, cap = self.config, C if capacity is None else int(capacity)
+            dt = torch.bfloat16 if self._act_dtypes()[1] else torch.float32
+            if pack == 'kv':
+                cache = GrowingKVCache(self, [GrowingKVCache.buffers(B, cap, L, c.d_model, dt, self.device) for _ in range(c.n_layer)],
+                                       B, C, tshape, cap)
+            else:
+                cache = GrowingE4M3Cache(self, [GrowingE4M3Cache.buffers(B, cap, c.n_head, self.device) for _ in range(c.n_layer)],
+                                         B, C, tshape, cap)
+            sink = PrefillSink(cache, C)
+            self._blocks(codes, self._pose_embed(cameras), B, C, L, kv_sink=sink)
+            sink.close()
+            return cache
         kv = []
         self._blocks(codes, self._pose_embed(cameras), B, C, L, kv_sink=kv)
         cache = ContextCache(self, kv, B, C, tshape)
@@ -408,14 +430,15 @@ class MIGT:
 
     def _context_args(self, what, cache, cameras=None, codes=None, n_context=None, one_photo=False, needs=None, view0=None, lengths=True):
         """The front matter of every method that takes a cache, in ``score_from_context``'s order: the cache (a ContextCache that can do
-        what ``needs`` — None, ``'room'`` or ``'backward'`` —, of a shape and arm with prefix-cache attention, of this model), the optional
-        ``cameras`` fp32 [B,N,7], the optional ``codes`` int [B,N,t,t] (``one_photo``: or [B,1,t,t]), sample's ``view0`` and ``n_context``
+        what ``needs`` — None, ``'room'`` or ``'backward'`` —, of a shape and arm with prefix-cache attention, of this model; ``'room'``
+        lets a plain cache, a fork and a GROWING packed cache through, never a read-only packed one), the optional ``cameras`` fp32
+        [B,N,7], the optional ``codes`` int [B,N,t,t] (``one_photo``: or [B,1,t,t]), sample's ``view0`` and ``n_context``
         -> (cameras and codes on the device, N, L, the context lengths as ``_context_lengths`` makes them, None without ``lengths``).
         Every refusal comes before any launch and before the one host-to-device copy of the lengths."""
         if not isinstance(cache, ContextCache):
             raise TypeError(f'{what}: a ContextCache from prefill_context expected')
         if needs is not None:
-            (cache.refuse_backward if needs == 'backward' else cache.refuse_packed)(what)
+            (cache.refuse_backward if needs == 'backward' else cache.refuse_growth if needs == 'room' else cache.refuse_packed)(what)
         B, tshape, L = cache.B, cache.tshape, cache.L
         self._check_render_shapes(L)                                         # an arm or shape without prefix-cache attention: refused whatever the cache
         cache.check(self)
@@ -877,6 +900,8 @@ class MIGT:
         noise keys and the fork as the returned ``cache`` (``adopt_from_fork`` keeps one trajectory in ``cache``)."""
         S = self._sampler_args('rollout_from_context', n_samples, temperature, top_k, top_p)
         path_cameras, _, T, L, _ = self._context_args('rollout_from_context', cache, path_cameras, needs='room', lengths=False)
+        if fork:
+            cache.refuse_packed('rollout_from_context(fork=True)')           # (a growing packed cache grows, but it is no fork's parent)
         c, dev = self.config, self.device
         d, nE, tshape, B = c.d_model, c.n_embeddings, cache.tshape, cache.B
         if T * L >= 1 << 32 or B * S >= 1 << 31:

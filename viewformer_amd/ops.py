@@ -695,6 +695,46 @@ def kv_append(qkv, cache, B, K, L, d, ld_src, ld_dst, cache_stride, capacity, po
     return cache
 
 
+def kv_append_split(qkv, k, v, B, K, L, d, ld_src, ld_k, ld_v, k_stride, v_stride, capacity, pos):
+    """``kv_append`` for a cache without a Q third (vf_kv_append_split): the K third of new view j of scene b goes to columns [0, d) of
+    view ``pos[b] + j`` of ``k`` (``capacity`` views of L rows per scene, leading dimension ``ld_k``, scenes ``k_stride`` elements apart),
+    the V third to the same rows of ``v`` (``ld_v``, ``v_stride``), bit for bit, bf16 or fp32 (one dtype for the three tensors).  One
+    launch; nothing else of ``k`` and ``v`` changes."""
+    if qkv.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'kv_append_split: bf16 or fp32 tensors expected, got {qkv.dtype}')
+    _chk(k, qkv.dtype, 'k')
+    _chk(v, qkv.dtype, 'v')
+    _chk(qkv, qkv.dtype, 'qkv')
+    _chk(pos, torch.int32, 'pos')
+    if pos.numel() != B or not pos.is_contiguous():
+        raise ValueError(f'kv_append_split: pos int32 [B = {B}] contiguous expected, got {tuple(pos.shape)}')
+    check(_lib.load().vf_kv_append_split(_p(qkv), _p(k), _p(v), qkv.element_size(), B, K, L, d, ld_src, ld_k, ld_v, k_stride, v_stride,
+                                         capacity, _p(pos), _stream()), 'vf_kv_append_split')
+    return k, v
+
+
+def kv_append_e4m3(qkv, kq, vq, kscale, vscale, B, K, H, L, ld_src, capacity, pos, q_view_stride=None, q_scene_stride=None,
+                   s_view_stride=None, s_scene_stride=None):
+    """The quantising ``kv_append`` (csrc/kv_append_e4m3.hip): the K and V thirds of new view j of scene b of ``qkv`` (fused c_attn rows
+    [B*K*L] of leading dimension ``ld_src``, bf16 or fp32) go to slot ``pos[b] + j`` of the packed buffers — e4m3 tiles and scales as
+    ``kv_pack_e4m3`` writes them for the same values, with its strides (default: tight [B*capacity, H, 64, 64] / [B*capacity, H]).
+    ``pos``: int32 device tensor [B]; a slot outside [0, capacity) is skipped.  One launch; nothing else changes."""
+    if qkv.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f'kv_append_e4m3: bf16 or fp32 rows expected, got {qkv.dtype}')
+    _chk(qkv, qkv.dtype, 'qkv')
+    _chk(kq, torch.uint8, 'kq')
+    _chk(vq, torch.uint8, 'vq')
+    _chk(kscale, torch.float32, 'kscale')
+    _chk(vscale, torch.float32, 'vscale')
+    _chk(pos, torch.int32, 'pos')
+    if pos.numel() != B or not pos.is_contiguous():
+        raise ValueError(f'kv_append_e4m3: pos int32 [B = {B}] contiguous expected, got {tuple(pos.shape)}')
+    qv, qs, sv, ss = _pack_strides(capacity, H, q_view_stride, q_scene_stride, s_view_stride, s_scene_stride)
+    check(_lib.load().vf_kv_append_e4m3(_p(qkv), qkv.element_size(), _p(kq), _p(vq), _p(kscale), _p(vscale), B, K, H, L, ld_src, qv, qs, sv, ss,
+                                        capacity, _p(pos), _stream()), 'vf_kv_append_e4m3')
+    return kq, vq, kscale, vscale
+
+
 def _pack_strides(C, H, q_view_stride, q_scene_stride, s_view_stride, s_scene_stride):
     """the tight packed layout [B*C, H, 64, 64] bytes / [B*C, H] scales where a stride is None"""
     qv = H * 4096 if q_view_stride is None else int(q_view_stride)

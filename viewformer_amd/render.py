@@ -175,7 +175,8 @@ def plan_capacity(capacity: int, needed: int) -> int:
 def plan_cache_bytes(B: int, C: int, L: int, d_model: int, n_head: int, n_layer: int, elem_bytes: int, form=None) -> int:
     """The bytes of a context cache of B scenes x C views of room, from its shapes (``ContextCache.nbytes``): ``form`` None = the plain
     cache ([B*C*L, 3 d] per layer), 'kv' = the K/V-only pack ([B*C*L, d] twice: exactly 2/3), 'e4m3' = the e4m3 pack (two byte tiles
-    [B*C, H, 64, 64] and two fp32 scales [B*C, H] per layer; ``elem_bytes`` does not enter).  Pure."""
+    [B*C, H, 64, 64] and two fp32 scales [B*C, H] per layer; ``elem_bytes`` does not enter).  A GROWING packed cache
+    (``pack(room=...)``) holds the same tensors with C = its ``capacity``: pass that.  Pure."""
     B, C, L, d, H, n = int(B), int(C), int(L), int(d_model), int(n_head), int(n_layer)
     if min(B, C, L, d, H, n) < 0 or int(elem_bytes) not in (2, 4):
         raise ValueError(f'plan_cache_bytes: sizes >= 0 and elem_bytes 2 or 4 expected, got {(B, C, L, d, H, n, elem_bytes)}')
@@ -273,7 +274,7 @@ class ViewRenderer:
         self.fused_score = None            # score: None = MIGT.score_from_context's default route, True / False = the fused LM head / through the logits
         self.fused_tail = None             # localize: None = MIGT.localize_from_context's default tail, True / False = the fused / unfused one
 
-    def set_context(self, images=None, cameras=None, codes=None, n_context=None, capacity=None):
+    def set_context(self, images=None, cameras=None, codes=None, n_context=None, capacity=None, pack=None):
         """``images`` uint8 [B,C,H,W,3] (host or device; resized for the encoder as the evaluators do) or ``codes`` int [B,C,t,t]
         (already encoded, e.g. ``SceneBank.gather``), and ``cameras`` [B,C,7] in the caller's world frame.  Encodes once, prefills the
         transformer's key / value cache once.  ``n_context``: [B] (or an int), the number of valid context views per scene in [1, C],
@@ -281,7 +282,10 @@ class ViewRenderer:
         ``sample``, ``score``, ``localize`` and ``sweep``).  Padding views must hold valid code ids (or images) and finite cameras; they
         are computed by the prefill and never read by a query.  View 0 is valid in every scene, so the poses' frame is each scene's own.
         ``capacity`` >= C: room for that many views per scene (``MIGT.prefill_context``), so that ``append`` and ``rollout`` need not
-        reallocate; None: the tight cache, which grows at the first of them."""
+        reallocate; None: the tight cache, which grows at the first of them.
+        ``pack``: None, ``'kv'`` or ``'e4m3'`` (bf16 models): the context is filled as a GROWING packed cache of that form directly
+        (``MIGT.prefill_context(pack=...)``: the plain cache never exists), as ``set_context(...)`` then ``pack(dtype, room=capacity - C)``
+        would leave it, bit for bit."""
         tm, cm = self.transformer, self.codebook
         dev = cm.device
         if cameras is None or (images is None) == (codes is None):
@@ -309,18 +313,23 @@ class ViewRenderer:
             if codes.numel() != B * C * t * t:
                 raise ValueError(f'set_context: codes {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
         codes = codes.to(torch.int32).view(B, C, t, t)
-        self.cache = tm.prefill_context(codes, poses) if capacity is None else tm.prefill_context(codes, poses, capacity=capacity)
+        kw = {} if pack is None else dict(pack=pack)
+        if capacity is not None:
+            kw['capacity'] = capacity
+        self.cache = tm.prefill_context(codes, poses, **kw)
         self.transform, self.context_codes, self.n_context = transform, codes, n_context
         return self
 
-    def pack(self, dtype=None):
+    def pack(self, dtype=None, room=None):
         """Pack the context in place (``ContextCache.pack``; the plain cache is released) and return ``self``: ``dtype=None`` keeps the
         K and V thirds as they are (2/3 of the bytes, both arms, every answer keeps its bits), ``dtype='e4m3'`` (bf16 models) stores
         them as e4m3 bytes with a power-of-two scale per (scene, view, head) — about 1/3 of the bf16 bytes, the answers of the bf16 arm
         on the dequantised cache.  ``render``, ``sample``, ``score``, ``localize`` and ``sweep`` go on working; ``append``, ``rollout``,
-        ``fork``, ``score_gradient`` and ``refine`` refuse until ``unpack()``."""
+        ``fork``, ``score_gradient`` and ``refine`` refuse until ``unpack()``.  ``room=R`` (an integer >= 0; opt-in): the GROWING packed
+        form with R views of slack per scene (``ContextCache.pack(room=...)``), on which ``append`` and ``rollout`` (``keep``,
+        ``n_samples``; not ``fork=True``) go on working; ``fork``, ``score_gradient`` and ``refine`` still refuse until ``unpack()``."""
         self._context('pack')
-        self.cache = self.cache.pack(dtype)
+        self.cache = self.cache.pack(dtype) if room is None else self.cache.pack(dtype, room=room)
         return self
 
     def unpack(self):
@@ -342,6 +351,9 @@ class ViewRenderer:
 
     def _refuse_packed(self, what):
         self.cache.refuse_packed(f'ViewRenderer.{what}')
+
+    def _refuse_growth(self, what):
+        self.cache.refuse_growth(f'ViewRenderer.{what}')
 
     def _own_lengths(self, cache):
         """before the context grows: a ragged batch's valid views (``set_context(n_context=...)``) become the cache's own lengths, so
@@ -370,7 +382,7 @@ class ViewRenderer:
         per scene in one pass over the new views (``MIGT.append_to_context``): no earlier view is run again.  Every later ``render``,
         ``sample``, ``score``, ``localize`` and ``sweep`` sees the grown context; ``n_context`` and ``context_codes`` follow."""
         self._context('append')
-        self._refuse_packed('append')
+        self._refuse_growth('append')
         if cameras is None or (images is None) == (codes is None):
             raise ValueError('append: cameras and exactly one of images / codes expected')
         tm, cm = self.transformer, self.codebook
@@ -436,7 +448,9 @@ class ViewRenderer:
         again), ``'best'`` being the one with the largest sum of ``log_likelihood`` over T, ties going to the lowest index;
         ``context_codes`` and ``n_context`` follow as with ``keep=True`` for S = 1, and the result gains ``adopted`` int64 [B]."""
         self._context('rollout')
-        self._refuse_packed('rollout')
+        self._refuse_growth('rollout')
+        if fork:
+            self._refuse_packed('rollout(fork=True)')
         if adopt is not None and not (fork and int(n_samples) > 1):
             raise ValueError('rollout: adopt goes with fork=True and n_samples > 1 (keep=True keeps the one trajectory of n_samples = 1)')
         if adopt is not None and isinstance(adopt, str) and adopt != 'best':
@@ -852,12 +866,13 @@ def sample_views(transformer_model, codebook_model, images, cameras, query_camer
 def rollout_views(transformer_model, codebook_model, images, cameras, path_cameras, **kw):
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``path_cameras`` [B,T,7] -> ``ViewRenderer.rollout``'s
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``n_context`` (valid context views per scene),
-    ``n_samples``, ``temperature``, ``top_k``, ``top_p``, ``seed``, ``return_codes``, ``fused_step``.  The cache is allocated with room
-    for the whole path."""
+    ``n_samples``, ``temperature``, ``top_k``, ``top_p``, ``seed``, ``return_codes``, ``fused_step``, ``pack`` (None, ``'kv'`` or
+    ``'e4m3'``: roll out on a growing packed context, ``set_context(pack=...)``).  The cache is allocated with room for the whole path."""
     T = int(torch.as_tensor(path_cameras).shape[1])
     C = int(torch.as_tensor(cameras).shape[1])
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None),
-                                                                    n_context=kw.pop('n_context', None), capacity=C + T)
+                                                                    n_context=kw.pop('n_context', None), capacity=C + T,
+                                                                    pack=kw.pop('pack', None))
     return r.rollout(path_cameras, **kw)
 
 
