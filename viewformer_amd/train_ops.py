@@ -433,6 +433,12 @@ def conv3_wgrad_supported(Cin, n_img, Hout, Wout):
     return Cin % 128 == 0 and pow2(Hout) and pow2(Wout) and Wout % 4 == 0 and (n_img * Hout * Wout) % 64 == 0
 
 
+def conv3_wgrad_splits(Cin, Cout, P):
+    """slabs conv3_wgrad splits the P = n_img * Hout * Wout reduction into (more than one: summed by vf_sum_slabs_f32)"""
+    tiles = (9 * (Cin // 128) + 1) * ((Cout + 127) // 128)
+    return max(1, min(256, 512 // tiles, P // 512))
+
+
 def conv3_wgrad(x, dy, n_img, Hin, Win, Cin, Hout, Wout, Cout, mode):
     """weight + bias gradient of a 3x3 convolution (forward mode ``mode``) -> [9*Cin + 1][Cout]: rows (ky*3+kx)*Cin + ci, last row
     = bias gradient.  x: NHWC input rows of the forward conv, dy: [P][Cout]."""
@@ -440,8 +446,7 @@ def conv3_wgrad(x, dy, n_img, Hin, Win, Cin, Hout, Wout, Cout, mode):
     lib = _lib.load()
     P = n_img * Hout * Wout
     rows = int(lib.vf_conv3_wgrad_x6_rows(Cin))
-    tiles = (9 * (Cin // 128) + 1) * ((Cout + 127) // 128)
-    splits = max(1, min(256, 512 // tiles, P // 512))
+    splits = conv3_wgrad_splits(Cin, Cout, P)
     dyp = ops.pack_dense_kn_x6(dy)
     slabs = torch.empty((splits, rows, Cout), dtype=torch.float32, device=x.device)
     check(lib.vf_conv3_wgrad_x6(_p(_f32(x)), _p(dyp), _p(slabs), n_img, Hin, Win, Cin, Hout, Wout, Cout, mode, splits, _stream()),
