@@ -201,9 +201,10 @@ int vf_colsumsq_f32(const float* E, float* e_sq, int D, int Kc, void* stream) {
 
 int vf_vq_argmin_f32(const float* z, const float* E_packed, const float* e_sq, int64_t M, int D, int Kc,
                      int64_t* idx, void* stream) {
-    if (!z || !E_packed || !e_sq || !idx || M < 0 || D <= 0 || Kc <= 0) return VF_ERR_BAD_ARG;
+    if (M < 0 || D <= 0 || Kc <= 0) return VF_ERR_BAD_ARG;
     if (D % CK != 0) return VF_ERR_UNSUPPORTED;
-    if (M == 0) return VF_OK;
+    if (M == 0) return VF_OK;                     // (an empty batch owns no memory: its pointers may be null)
+    if (!z || !E_packed || !e_sq || !idx) return VF_ERR_BAD_ARG;
     const size_t smem = (size_t)(2 * BM * A_LD + 2 * CK * BN + BM) * sizeof(float);
     static unsigned long long attr_devs = 0;      // bit d: raised on device d (the attribute is per device)
     if (vf_attr_needed(&attr_devs)) {
@@ -219,8 +220,9 @@ int vf_vq_argmin_f32(const float* z, const float* E_packed, const float* e_sq, i
 }
 
 int vf_codebook_gather_f32(const float* E, const int64_t* idx, float* out, int64_t M, int D, int Kc, void* stream) {
-    if (!E || !idx || !out || M < 0 || D <= 0 || Kc <= 0) return VF_ERR_BAD_ARG;
-    if (M == 0) return VF_OK;
+    if (M < 0 || D <= 0 || Kc <= 0) return VF_ERR_BAD_ARG;
+    if (M == 0) return VF_OK;                     // (an empty batch owns no memory: its pointers may be null)
+    if (!E || !idx || !out) return VF_ERR_BAD_ARG;
     hipLaunchKernelGGL(gather_kernel, dim3((unsigned)M), dim3(64), 0, (hipStream_t)stream, E,
                        reinterpret_cast<const long long*>(idx), out, (long long)M, D, Kc);
     return vf_last_status();
