@@ -30,7 +30,7 @@ the learned log-variance pair ``pose_loss_weighting_criterion.pos_ori_weights`` 
 batch (reduce_sum, :117) while every other term is a batch mean; restated as is.
 """
 import math
-import re
+from collections import namedtuple
 from typing import NamedTuple
 
 import numpy as np
@@ -220,7 +220,7 @@ def step_plan(cfg, precision, B, S, L, NS, rate=0.0, row0=0, **switches):
     here = at(M, row0)
     # prune_last_block: the losses read the branch streams only (MASK -> LM head, LOC -> pose head: migt.py:416-448); every block but the last
     # needs the main stream's rows as keys and values of the next one, the LAST block's projection / LayerNorm / MLP on them feed nothing (see
-    # train_step).  Mx = B (NS - 1) S L rows need not tile like M: with NS = 2 and an odd B * S, Mx % 128 == 64; with B * S = 2, Mx = 128 is
+    # MIGTTrainer._block_rows).  Mx = B (NS - 1) S L rows need not tile like M: with NS = 2 and an odd B * S, Mx % 128 == 64; with B * S = 2, Mx = 128 is
     # under the 256-tile kernels' minimum.  The step is pruned only where the plan taken at M holds at Mx as well
     tail = bool(sw['prune_last_block'] and NS > 1 and cfg.n_layer > 0)
     if tail:
@@ -236,7 +236,142 @@ def step_plan(cfg, precision, B, S, L, NS, rate=0.0, row0=0, **switches):
                     gelu_bwd16=here['grad16'] and sw['fuse_gelu_backward'], u16=u16, gelu_derivative=u16 and sw['save_gelu_derivative'])
 
 
+class Step(NamedTuple):
+    """what every phase of one train_step call needs: the shapes, the dropout rate / seed and this rank's position in the global batch,
+    the StepPlan.  Built once per step (MIGTTrainer._begin_step)."""
+    B: int
+    S: int
+    L: int
+    NS: int                 # streams: main, MASK (, LOC)
+    V: int                  # NS * S views per scene
+    Tn: int                 # V * L tokens per scene
+    M: int                  # B * Tn rows
+    M1: int                 # B * S * L rows of one stream
+    Mx: int                 # rows from the last block's projection on (StepPlan.Mx)
+    rate: float             # 0.0 outside training: Dropout layers are inert with training=False
+    seed: int
+    row0: int               # this rank's first row ...
+    plane0: int             # ... and first attention plane in the global batch
+    plan: StepPlan
+    training: bool
+
+    def drop(self, site):
+        """the dropout tuple of an elementwise site at all M rows"""
+        return (self.rate, self.seed, site, self.row0)
+
+    def drop_branch(self, site):
+        """... at the Mx rows of the pruned last block and ln_f: the masks there are indexed by the gathered rows"""
+        return (self.rate, self.seed, site, self.row0 // self.NS * (self.NS - 1)) if self.plan.tail else self.drop(site)
+
+    def drop_attn(self, i):
+        """... of block i's attention weights (a plane offset)"""
+        return (self.rate, self.seed, site_attn(i), self.plane0)
+
+    def branch_rows(self, x):
+        """the NS - 1 branch streams' rows of x [M][C] (contiguous per scene), gathered: [Mx][C]"""
+        return x.view(self.B, self.NS, self.S * self.L, -1)[:, 1:].reshape(self.Mx, -1)
+
+    def scatter_branch_rows(self, x):
+        """the inverse for a gradient: back to [M][C] with zeros in the main stream's rows (nothing downstream of them reached a loss)"""
+        full = torch.zeros((self.B, self.NS, self.S * self.L, x.shape[-1]), dtype=x.dtype, device=x.device)
+        full[:, 1:] = x.view(self.B, self.NS - 1, self.S * self.L, x.shape[-1])
+        return full.view(self.M, x.shape[-1])
+
+
+class BlockSaved(NamedTuple):
+    """what a transformer block keeps for its backward"""
+    h: torch.Tensor         # the block's input (all M rows)
+    n1: torch.Tensor        # ln_1(h)
+    qkv: torch.Tensor
+    att: torch.Tensor       # the attention output at all rows ...
+    att_i: torch.Tensor     # ... and at the rows attn.c_proj ran on (the branch rows in the pruned last block)
+    h_mid: torch.Tensor     # h + resid_dropout(c_proj(att))
+    n2: torch.Tensor        # ln_2(h_mid)
+    u: torch.Tensor         # c_fc's pre-activation (or gelu'(u): u_deriv)
+    f: torch.Tensor         # gelu(u)
+    lse: torch.Tensor       # the attention's log-sum-exp
+    u_deriv: bool
+
+
+EmbedSaved = namedtuple('EmbedSaved', 'pin u1 h1 ids32 tok rmul')                      # the embedding phase's values for the losses / backward
+HeadsSaved = namedtuple('HeadsSaved', 'hmask dlogits lm16 pose')                       # the losses' values for the heads' backward; pose: None or
+PoseSaved = namedtuple('PoseSaved', 'hloc up p1 small_n draw')                          # the pose head's
+
+
+def qkv_thirds(t, d):
+    """the (Q, K, V) column thirds of a fused [M][3 d] tensor — stored as (V, Q, K), migt.py:207-213; gradients land in the same thirds —
+    and their three leading dimensions"""
+    return (t[:, d:2 * d], t[:, 2 * d:], t[:, :d]), (3 * d, 3 * d, 3 * d)
+
+
 class MIGTTrainer:
+    # ------------------------------------------------------------------ switches: the ones step_plan reads, in PLAN_SWITCHES' order ...
+    attention_arith = 'bf16'          # bf16 arm only: 'bf16' = attention forward / backward on the bf16 matrix pipe; 'f32' = the exact-f32 kernels
+    bf16_saved_activations = True     # bf16 arm: LayerNorm outputs / MLP hidden saved as bf16 (see step_plan); False keeps them fp32 (same gradients)
+    bf16_gradient_operands = True     # bf16 arm: gelu_bwd / attention backward write their gradients as bf16 (see step_plan)
+    tn_weight_gradient = True         # bf16 arm: dW / db of the wide layers straight from the row-major operands (False: transpose + pack + column sums)
+    bf16_residual_gradient = True     # bf16 arm: the LayerNorm backward also writes its result as bf16 — the operand of the two projection
+                                      # layers' backward GEMMs, which then run on the 256-tile kernel (the rounding is the one the GEMM's operand
+                                      # load applied anyway; only the two bias gradients see it)
+    fuse_gelu_forward = True          # bf16 arm: c_fc writes u (fp32, saved) and bf16 gelu(u) from one epilogue (VF_EPI_GELU_DUAL); the GELU there
+                                      # is the inference arm's vf_gelu_erf_fast (|err| 1.5e-7: a few outputs round to the neighbouring bf16)
+    fuse_gelu_backward = True         # bf16 arm: d(pre-activation) = dX(mlp.c_proj) * gelu'(u) in that GEMM's epilogue (same bits as the two passes)
+    bf16_preactivation = True         # bf16 arm, with both GELU fusions: c_fc's pre-activation u is SAVED as bf16 (the reference's mixed_float16 policy
+                                      # keeps every activation in half precision); gelu(u) is still taken from the fp32 accumulator, gelu'(u)
+                                      # in the backward epilogue from the rounded u.  False: u saved as fp32.
+    save_gelu_derivative = True       # bf16 arm, with bf16_preactivation: what c_fc saves for the backward is gelu'(u) (bf16, from the erf / exp evaluation its GELU
+                                      # makes anyway: three more instructions per element) instead of u, whose only reader — the GELU-backward epilogue of the
+                                      # mlp.c_proj dX GEMM — then multiplies by a loaded value instead of evaluating erf + exp per element again (that epilogue
+                                      # was 22 us of a 148 us launch).  gelu' is taken from the fp32 pre-activation and rounded once; before it was evaluated
+                                      # on the bf16-rounded u
+    fuse_dropout = True               # bf16 arm: residual / MLP dropout in the projection GEMM's epilogue and in the LayerNorm backward's bf16 copy
+                                      # (False: the separate dropout_add passes; the same masks, the same values up to the GEMM's own rounding)
+    prune_last_block = True           # the last block's projection / LayerNorm / MLP (forward and backward) and ln_f on the branch streams' rows only: the main
+                                      # stream's rows of the last block reach no loss (see _block_rows); its dropout masks there are indexed by the gathered rows
+    # ... and the rest
+    overlap_weight_gradients = True   # bf16 arm: the TN weight-gradient GEMM of a layer on a second stream beside that layer's dX GEMM
+    serial_wgrad_split_as_overlapped = False      # (see _weight_gradient)
+    early_optimizer = False           # (measured in round 6: 19.660 vs 19.665 ms per step — the update hides, and the backward beside it slows by as much: off)
+                                      # bf16 arm: a layer's AdamWeightDecay update and the re-packing of its weights are issued on a third stream as soon as
+                                      # that layer's gradients are final (its backward and weight-gradient GEMMs done, its all-reduce complete) — HBM-bound
+                                      # work beside the matrix-bound backward of the layers below instead of 0.65 ms at the end of the step.  Same kernels on
+                                      # the same values: the parameters after a step are bit-identical (tests/test_train.py)
+    fused_optimizer = True            # AdamWeightDecay as ONE launch over the flat buffer (False: one launch per tensor, 468 per step; bit-identical)
+    fused_optimizer_repack = True     # bf16 arm: the optimizer step writes the dense layers' bf16 packings from the updated weights in the same pass
+                                      # (vf_adamw_flat_pack_f32) instead of a re-pack launch that reads every weight again twice; bit-identical
+    one_launch_repack = True          # bf16 arm: all weight packings refreshed by one launch per step
+    lazy_gradient_zero = True         # the transformer layers' gradient tensors (85 M of the 88 M) are not zero-filled at the start of a step: each is written
+                                      # exactly once per step, so its first writer STORES (sum_slabs / LayerNorm backward with accumulate off) instead of adding
+                                      # to a zero — one 337 MB fill and one 337 MB read of zeros less per step.  Keys still unset when a layer's (or the
+                                      # step's) backward ends are zero-filled then, so a tensor no kernel wrote is a zero gradient, as before.  The head range
+                                      # (embeddings, pose heads, ln_f: several contributions each) is zero-filled as before.  Same bits: x + 0 == x.
+    small_n_pose_head = True          # the pose head's 1536 -> 7 layer and its dW on the one-pass small-N kernels (False: the implicit-GEMM kernel, round 5)
+    bf16_lm_head = True               # bf16 arm: the tied LM head (logits, dH, dwte) on the bf16 pipe like every other wide layer (the native-f32
+                                      # GEMMs it replaces were 0.8 ms of a 21 ms step); False: native f32 MFMA
+    attention_backward = 'flash'      # 'dense': the first version (P materialised per head with batched GEMMs), kept for A/B
+    scene_offset = None               # index of this rank's first scene in the GLOBAL batch of a data-parallel step (None: rank * local batch).
+                                      # Every random draw of the step — the dropout masks, the random pose multiplier — is a function of
+                                      # the GLOBAL scene index, so N ranks draw exactly what one process draws on the concatenated batch,
+                                      # and no two replicas share a mask (with one seed per step and local indices they all would)
+    grad_allreduce_dtype = 'f32'      # 'bf16': each range is all-reduced as a bf16 copy (177 MB instead of 354 MB on the links; the sum
+                                      # of the replicas' gradients is then rounded to 8 bits per replica term — an option, off by default:
+                                      # the reference's MirroredStrategy reduces fp32 variables' gradients in fp32)
+    time_allreduce = False            # record HIP events around the wait for the collectives (exposed_allreduce_ms())
+    # ------------------------------------------------------------------ what the trainer caches between steps
+    _pack16 = None                    # the one-launch refresh of every bf16 packing (ops.pack_bf16_multi's closure), _pack16_keep its tensors,
+    _pack16_keep = None               # _adam_pack the same packings as destinations of the fused optimizer, _layer_pack_ranges the table's
+    _adam_pack = None                 # descriptor range per transformer layer (_build_pack_tables)
+    _layer_pack_ranges = None
+    _packs_fresh = False              # apply_gradients' fused optimizer wrote the packings with the update: the next repack skips them
+    _lm16 = None                      # the tied LM head's two bf16 packings
+    lm_T = None                       # ... and its native transposed packing (_pack_lm_T)
+    _lm_T_stale = True
+    _side_busy = False                # a weight-gradient GEMM is in flight on the 'side' stream (_join_side)
+    _unset = frozenset()              # lazy_gradient_zero: the layer tensor pairs no kernel has written yet this step
+    _layer_grad_keys = None
+    _allreduce_events = None
+    last_plan = None                  # the StepPlan of the last train_step call
+
     def __init__(self, model: MIGT, warmup_steps: int = 2000, beta1: float = 0.9, beta2: float = 0.999,
                  eps: float = 1e-8, process_group=None):
         cfg = model.config
@@ -256,6 +391,8 @@ class MIGTTrainer:
         self.lr_offset = 0                           # WarmUp.offset (models/utils.py:337): begin_finetune() moves it
         self.lr_init, self.lr_total_steps = cfg.learning_rate, cfg.total_steps     # create_optimizer's arguments (train_transformer.py)
         self.loc_weight = parse_schedule(cfg.localization_weight, cfg.total_steps)
+        self.wpT, self.wpT6, self.wpT16 = {}, {}, {}     # transposed packings per dense layer: native f32, split (x6), bf16
+        self._streams, self._nodecay = {}, {}            # _stream(name), _nodecay_table(a, b)
         self._layout()
         self._bind()
 
@@ -308,122 +445,127 @@ class MIGTTrainer:
 
     def _bind(self):
         """point the model's tensors at the flat buffer and (re)build every packed weight"""
-        m, c = self.model, self.cfg
-        m._wte, m._wpe = self.p('wte.weight'), self.p('wpe.embeddings')
+        m = self.model
+        m._wte, m._wpe =self.p('wte.weight'), self.p('wpe.embeddings')
         for name, dn in m._dense.items():
             dn.w_raw, dn.bias = self.p(name + '.weight'), self.p(name + '.bias')
         for name in list(m._ln):
             m._ln[name] = (self.p(name + '.gamma'), self.p(name + '.beta'))
-        self.wpT = getattr(self, 'wpT', {})
         self.repack()
 
-    def repack(self):
+    def repack(self, early_layers_done: bool = False):
         """refresh every packed form of the (just updated) weights: native-f32 packings always (odd shapes, the LM head, the
         pose heads), and with ``dense_arith='x6'`` the fp32-equivalent split packings the dense layers actually run on —
-        forward W, and W^T for dX (x6 GEMMs are ~1.8x the native ones; the packers are a few launches per layer)"""
-        m, c = self.model, self.cfg
-        nE, d = c.n_embeddings, c.d_model
+        forward W, and W^T for dX (x6 GEMMs are ~1.8x the native ones; the packers are a few launches per layer).  ``early_layers_done``
+        (apply_gradients): the transformer layers' bf16 packings were refreshed right after their early update"""
+        m, nE, d = self.model, self.cfg.n_embeddings, self.cfg.d_model
         bf16 = m.precision == 'bf16'          # the reference trains with --fp16 (mixed_float16): bf16 MFMA, fp32 master weights
         x6 = m.dense_arith in ('x6', 'x3h') and not bf16
         x3h = m.dense_arith == 'x3h'          # forward activations only; dX / dW (gradient magnitudes) stay on x6
-        self.wpT6 = getattr(self, 'wpT6', {})
-        self.wpT16 = getattr(self, 'wpT16', {})
-        m._lm_head16 = None
-        m._lm_head6 = None                                  # the LM head / pose heads stay on the native kernel in training
-        # bf16 arm: after the first call (which allocates the packings one by one) every layer's W and W^T packing is refreshed by ONE
-        # launch over a descriptor table (96 pack launches per step before)
+        m._lm_head16 = m._lm_head6 = None                   # the LM head / pose heads stay on the native kernel in training
         lm16 = bf16 and self.bf16_lm_head and d % 256 == 0 and nE % 256 == 0
         if lm16 and self._lm16 is None:
-            self._pack16 = None                                  # (the LM-head packings join the descriptor table: rebuild it)
-            self._adam_pack = None
+            self._pack16 = self._adam_pack = None                # (the LM-head packings join the descriptor table: rebuild it)
         if self._pack16 is not None and (not bf16 or any(
                 dn.wp16 is None or name not in self.wpT16 for name, dn in m._dense.items()
                 if dn.k % 128 == 0 and dn.n % 128 == 0)):
             # the table holds raw pointers into packings that are gone (the arm was switched to f32 and back, or a layer lost its
             # buffers): never run it against them — rebuild from scratch below
-            self._pack16 = None
-            self._pack16_keep = None
-            self._layer_pack_ranges = None
-            self._adam_pack = None
+            self._pack16 = self._pack16_keep = self._layer_pack_ranges = self._adam_pack = None
+        # bf16 arm: after the first call (which allocates the packings one by one and builds the tables: _build_pack_tables) every layer's W and
+        # W^T packing is refreshed by ONE launch over a descriptor table (96 pack launches per step before)
+        tables = self._pack16 is not None
         packs_fresh, self._packs_fresh = self._packs_fresh, False
-        if self._pack16 is not None and not packs_fresh:          # (fresh: apply_gradients' fused optimizer wrote them with the update)
-            if self._early_layers_done and self._layer_pack_ranges is not None:
-                # the layers' packings were refreshed right after their early update (train_step): only the rest of the table here
-                lo = min(a for a, n_ in self._layer_pack_ranges)
-                hi = max(a + n_ for a, n_ in self._layer_pack_ranges)
-                self._pack16(0, lo)
-                self._pack16(hi, None)
+        if tables and not packs_fresh:                            # (fresh: apply_gradients' fused optimizer wrote them with the update)
+            if early_layers_done and self._layer_pack_ranges is not None:      # only the rest of the table here
+                self._pack16(0, min(a for a, n_ in self._layer_pack_ranges))
+                self._pack16(max(a + n_ for a, n_ in self._layer_pack_ranges), None)
             else:
                 self._pack16()
-        pack_items, pack_names = [], []
+        new = []                                                  # (name, source, transposed, packing) of the bf16 packings allocated here
         for name, dn in m._dense.items():
             k32 = dn.k % 32 == 0
             to16 = bf16_packed(m.precision, dn.k, dn.n)
             to6 = x6 and k32 and dn.k % 64 == 0 and dn.n % 64 == 0
             # the native-f32 packings are refreshed only where no faster arm applies (they were 477 pack launches per step that nothing
             # read: the wide layers run on their bf16 / split packings); the transposed native packing of a wide layer is built on demand
-            # in _linear_bwd for row counts its arm does not tile
+            # in _linear_dx for row counts its arm does not tile
             dn.wp = ops.pack(dn.w_raw, dn.k, dn.n, 1, sk=dn.n, sn=1, st=0, out=dn.wp) if k32 and not (to16 or to6) else None    # forward: x @ W
             if dn.n % 32 == 0 and not (to16 or to6):                                                          # dX = dY @ W^T
                 self.wpT[name] = ops.pack(dn.w_raw, dn.n, dn.k, 1, sk=1, sn=dn.n, st=0, out=self.wpT.get(name))
             else:
                 self.wpT.pop(name, None)
-            keep16 = dn.wp16 if (to16 and self._pack16 is not None) else None
-            dn.wp6 = dn.wp16 = None
-            if to16:
-                if self._pack16 is not None:                          # buffers of the one-launch refresh below: filled there
-                    dn.wp16 = keep16
-                else:
-                    dn.wp16 = ops.pack_dense_kn_bf16(dn.w_raw)
-                    self.wpT16[name] = ops.pack_dense_nk_bf16(dn.w_raw)
-                    pack_items += [(dn.w_raw, False, dn.wp16), (dn.w_raw, True, self.wpT16[name])]
-                    pack_names += [name, name]
+            dn.wp6 = None
+            if not to16:
+                dn.wp16 = None
+            elif not tables:                                      # (with the tables: the buffers of the one-launch refresh above)
+                dn.wp16, self.wpT16[name] = ops.pack_dense_kn_bf16(dn.w_raw), ops.pack_dense_nk_bf16(dn.w_raw)
+                new += [(name, dn.w_raw, False, dn.wp16), (name, dn.w_raw, True, self.wpT16[name])]
             if to6:
                 dn.wp6 = ops.pack_dense_kn_x3h(dn.w_raw) if x3h else ops.pack_dense_kn_x6(dn.w_raw)
                 self.wpT6[name] = ops.pack_dense_nk_x6(dn.w_raw)          # [K][N] read as the transposed [N][K] operand
-        if lm16 and self._lm16 is None:                              # tied LM head on the bf16 pipe: logits = h @ wte^T, dH = dlogits @ wte
-            head = m._wte[:nE]
+        if lm16 and not tables:                                      # tied LM head on the bf16 pipe: logits = h @ wte^T, dH = dlogits @ wte
+            head, first = m._wte[:nE], self._lm16 is None            # (not the first: the per-tensor refresh, one_launch_repack off)
             self._lm16 = (ops.pack_dense_nk_bf16(head), ops.pack_dense_kn_bf16(head))
-            pack_items += [(head, True, self._lm16[0]), (head, False, self._lm16[1])]
-            pack_names += ['wte', 'wte']
-        elif lm16 and self._pack16 is None:                          # (per-tensor refresh: one_launch_repack off)
-            head = m._wte[:nE]
-            self._lm16 = (ops.pack_dense_nk_bf16(head), ops.pack_dense_kn_bf16(head))
-        if bf16 and self._pack16 is None and pack_items and self.one_launch_repack:
-            self._pack16 = ops.pack_bf16_multi(pack_items)          # (re-packs once more; from now on the closure is the refresh)
-            self._pack16_keep = pack_items                          # (the closure holds raw pointers: keep the tensors alive with it)
-            # the same packings as destinations of the fused optimizer (apply_gradients): one descriptor per weight matrix with both of its
-            # packed forms; None when a packing's source is not a whole [rows][cols] view of the flat buffer or a shape does not tile
-            by_src, ok = {}, True
-            for w, tr, out in pack_items:
-                e = by_src.setdefault(w.data_ptr(), [w, None, None])
-                ok = ok and e[0].shape == w.shape and e[2 if tr else 1] is None
-                e[2 if tr else 1] = out
-            if self._nodecay is None:
-                r = [[self.slices[n][0], self.slices[n][1]] for n in self.names if 'bias' in n]
-                self._nodecay = torch.tensor(sorted(r), dtype=torch.int64, device=self.dev).reshape(-1, 2)
-            self._adam_pack = T.adamw_pack_table(self.flat_p, [tuple(e) for e in by_src.values()], self._nodecay) if ok else None
-            # descriptor ranges per transformer layer (early_optimizer: a layer's weights are re-packed as soon as they are updated); valid only
-            # when every layer's descriptors are contiguous and every wide layer weight is in the table
-            rng, ok = [], True
-            for i in range(c.n_layer):
-                idx = [j for j, nm in enumerate(pack_names) if nm.startswith(f'h.{i}.')]
-                ok = ok and len(idx) == 8 and idx == list(range(idx[0], idx[0] + 8))
-                rng.append((idx[0], len(idx)) if idx else (0, 0))
-            self._layer_pack_ranges = rng if ok else None
+            if first:
+                new += [('wte', head, True, self._lm16[0]), ('wte', head, False, self._lm16[1])]
+        if bf16 and not tables and new and self.one_launch_repack:
+            self._build_pack_tables(new)
         m._lm_head = ops.pack(m._wte, d, nE, 1, sk=1, sn=d, st=0, out=m._lm_head)                          # logits = h @ wte^T (kept fresh for
         if not lm16:                                                                                      # whoever reads the model afterwards)
-            self.lm_T = ops.pack(m._wte, nE, d, 1, sk=d, sn=1, st=0, out=getattr(self, 'lm_T', None))       # dH = dlogits @ wte
-            self._lm_T_stale = False
+            self._pack_lm_T()
         else:
             self._lm_T_stale = True           # the step's own predicate also needs M1 % 64 == 0: its fallback must re-pack from THESE weights
+
+    def _build_pack_tables(self, new):
+        """the descriptor tables over the bf16 packings ``new`` = [(name, source, transposed, packing)] that repack just allocated (its first
+        bf16 call, or the first after the tables were invalidated): from now on _pack16 is the refresh"""
+        pack_items = [item[1:] for item in new]
+        self._pack16 = ops.pack_bf16_multi(pack_items)          # (re-packs once more)
+        self._pack16_keep = pack_items                          # (the closure holds raw pointers: keep the tensors alive with it)
+        # the same packings as destinations of the fused optimizer (apply_gradients): one descriptor per weight matrix with both of its
+        # packed forms; None when a packing's source is not a whole [rows][cols] view of the flat buffer or a shape does not tile
+        by_src, ok = {}, True
+        for w, tr, out in pack_items:
+            e = by_src.setdefault(w.data_ptr(), [w, None, None])
+            ok = ok and e[0].shape == w.shape and e[2 if tr else 1] is None
+            e[2 if tr else 1] = out
+        nodecay = self._nodecay_table(0, self.total)
+        self._adam_pack = T.adamw_pack_table(self.flat_p, [tuple(e) for e in by_src.values()], nodecay) if ok else None
+        # descriptor ranges per transformer layer (early_optimizer: a layer's weights are re-packed as soon as they are updated); valid only
+        # when every layer's descriptors are contiguous and every wide layer weight is in the table
+        rng, ok = [], True
+        for i in range(self.cfg.n_layer):
+            idx = [j for j, item in enumerate(new) if item[0].startswith(f'h.{i}.')]
+            ok = ok and len(idx) == 8 and idx == list(range(idx[0], idx[0] + 8))
+            rng.append((idx[0], len(idx)) if idx else (0, 0))
+        self._layer_pack_ranges = rng if ok else None
+
+    def _pack_lm_T(self):
+        """the tied LM head's native transposed packing (dH = dlogits @ wte), from the current weights"""
+        c = self.cfg
+        self.lm_T = ops.pack(self.model._wte, c.n_embeddings, c.d_model, 1, sk=c.d_model, sn=1, st=0, out=self.lm_T)
+        self._lm_T_stale = False
+
+    def _nodecay_table(self, a, b):
+        """device int64 [R][2]: the 'bias' tensors (models/utils.py:424: the only names excluded from the decay) that start inside elements
+        [a, b) of the flat buffer, as sorted ranges relative to a — cached per range"""
+        if (a, b) not in self._nodecay:
+            r = [[s - a, e - a] for s, e in sorted(self.slices[n][:2] for n in self.names if 'bias' in n) if a <= s < b]
+            self._nodecay[a, b] = torch.tensor(r, dtype=torch.int64, device=self.dev).reshape(-1, 2)
+        return self._nodecay[a, b]
+
+    def _adamw_args(self, a=0, b=None):
+        """the arguments of T.adamw_flat_ / adamw_flat_pack_ over elements [a, b) of the flat buffers (default: all of them)"""
+        b, wd = self.total if b is None else b, self.cfg.weight_decay
+        nodecay = self._nodecay_table(a, b)
+        lr, lr_adam = self._adam_scalars()
+        return (self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], nodecay if wd > 0 else None, lr * wd if wd > 0 else 0.0,
+                lr_adam, self.b1, self.b2, self.eps)
 
     # ------------------------------------------------------------------ building blocks
     def _linear(self, x, name, M, res=None):
         return self.model._gemm(x, name, M, res=res)
-
-    fuse_dropout = True               # bf16 arm: residual / MLP dropout in the projection GEMM's epilogue and in the LayerNorm backward's bf16 copy
-                                      # (False: the separate dropout_add passes; the same masks, the same values up to the GEMM's own rounding)
 
     def _proj_dropout(self, x, name, M, res, drop, fused=False):
         """res + dropout(x @ W + b)  (attn.c_proj -> resid_dropout, migt.py:216; mlp.c_proj -> the MLP's dropout, :72).  ``fused``
@@ -442,21 +584,25 @@ class MIGTTrainer:
         """grads of y = x @ W + b given dy [M,N]; returns dx (+res) or None.  ``x`` may be a saved bf16 activation (bf16 arm);
         ``dx_bf16``: the bf16 arm's dX GEMM writes bf16 (the attention backward's dO operand); ``gelu_bwd_u``, ``u_is_derivative``: see
         _linear_dx."""
+        self._weight_gradient(name, x, dy, M, need_dx)
+        return self._linear_dx(name, dy, M, res, dx_bf16, gelu_bwd_u, u_is_derivative) if need_dx else None
+
+    def _weight_gradient(self, name, x, dy, M, dx_follows):
+        """dW and db of y = x @ W + b into the layer's gradient pair; ``dx_follows``: the layer's dX GEMM is issued next"""
         dn = self.model._dense[name]
         K, N = dn.k, dn.n
         bf16 = name in self.wpT16 and dn.wp16 is not None and M % 128 == 0
         first = self._first_write(name)                   # (lazy_gradient_zero: this layer's gradient pair holds last step's values, not zeros)
+        gw, gb = self.g(name + '.weight'), self.g(name + '.bias')
         if bf16 and self.tn_weight_gradient and ops.gemm_tn_bf16_supported(x, M, K, N):
             # bf16 arm with a saved bf16 activation: dW and db in ONE pass over x and dy as they lie (csrc/gemm_tn_bf16.hip) — no widening
             # transpose of x, no packed bf16 copy of dy, no column-sum pass
-            gw, gb = self.g(name + '.weight'), self.g(name + '.bias')
-            if self.overlap_weight_gradients and need_dx:
+            if self.overlap_weight_gradients and dx_follows:
                 # ... on a SECOND HIP stream, beside the dX GEMM that reads the same dy: both are one under-filled round of 256-tile
                 # workgroups (225-243 on 256 CUs, one per CU: 128 KB of LDS each), so the weight gradient's workgroups take the CUs the
                 # dX GEMM leaves idle and its tail.  Joined before anything reads the layer's gradients (_join_side)
-                main = torch.cuda.current_stream(self.dev)
-                side = self._side()
-                side.wait_stream(main)                                                 # dy (and x) are complete
+                side = self._stream('side')
+                side.wait_stream(torch.cuda.current_stream(self.dev))                  # dy (and x) are complete
                 with torch.cuda.stream(side):
                     ops.gemm_tn_bf16(x, dy, M, K, N, gw, gb, accumulate=not first, beside_another_gemm=True)
                 for t in (x, dy):
@@ -465,34 +611,27 @@ class MIGTTrainer:
             else:
                 # (alone on the compute stream the launch takes the full-machine split, another summation order; serial_wgrad_split_as_overlapped
                 # keeps the second stream's split, for bit-for-bit comparisons of the two modes)
-                ops.gemm_tn_bf16(x, dy, M, K, N, gw, gb, accumulate=not first, beside_another_gemm=self.serial_wgrad_split_as_overlapped and need_dx)
-            return self._linear_dx(name, dy, M, res, dx_bf16, gelu_bwd_u, u_is_derivative) if need_dx else None
+                ops.gemm_tn_bf16(x, dy, M, K, N, gw, gb, accumulate=not first, beside_another_gemm=self.serial_wgrad_split_as_overlapped and dx_follows)
+            return
         if dy.dtype != torch.float32:
             raise RuntimeError('a bf16 gradient operand needs the TN weight-gradient path')
         if first:                                          # the paths below accumulate
-            self.g(name + '.weight').zero_()
-            self.g(name + '.bias').zero_()
-        T.colsum(dy, self.g(name + '.bias'), M, N, accumulate=True)
+            gw.zero_()
+            gb.zero_()
+        T.colsum(dy, gb, M, N, accumulate=True)
         Mp = (M + 31) // 32 * 32                                                     # reduction length padded to the K stage
-        xt = None
-        if Mp != M:
-            xt = torch.zeros((1, K, Mp), dtype=torch.float32, device=x.device)
-        xt = T.transpose(x, M, K, out=xt, ld_dst=Mp)                                 # [K][Mp]
-        gw = self.g(name + '.weight')
-        x6 = name in self.wpT6 and dn.wp6 is not None and M % 64 == 0
+        xt = T.transpose(x, M, K, out=torch.zeros((1, K, Mp), dtype=torch.float32, device=x.device) if Mp != M else None, ld_dst=Mp)      # [K][Mp]
+        # dW += X^T dY: [K][N] has only (K/128)(N/128) = 36..144 output tiles for 256 CUs but a reduction of M = 19 200 rows -> split-K on
+        # the bf16 and x6 arms; the bf16 split count must cut M into whole 64-row chunks of the packing
+        tiles = ((K + 127) // 128) * ((N + 127) // 128)
         if bf16:
-            # dW += X^T dY: (K/128)(N/128) = 36..144 output tiles for 256 CUs and a reduction of M = 19 200 rows -> split-K (as the x6
-            # arm below); the split count must cut M into whole 64-row chunks of the packing
-            tiles = ((K + 127) // 128) * ((N + 127) // 128)
             want = max(1, min(16, 768 // tiles))
             splits = max([s for s in range(1, want + 1) if M % (64 * s) == 0] or [1])
             if splits > 1 and (K * N) % 4 == 0:
                 ops.gemm_bf16_splitk(xt, ops.pack_dense_kn_bf16(dy), K, M, N, gw, splits, lda=Mp)
             else:
                 ops.igemm(xt, ops.pack_dense_kn_bf16(dy), K, M, N, gw, res=gw, lda=Mp, bf16=True)
-        elif x6:
-            # dW += X^T dY: [K][N] has only (K/128)(N/128) = 36..144 tiles for 256 CUs but a reduction of M = 19200 rows
-            tiles = ((K + 127) // 128) * ((N + 127) // 128)
+        elif name in self.wpT6 and dn.wp6 is not None and M % 64 == 0:
             splits = max(1, min(16, 768 // tiles, M // 1024))
             if splits > 1 and (K * N) % 4 == 0:
                 ops.gemm_x6_splitk(xt, ops.pack_dense_kn_x6(dy), K, M, N, gw, splits, lda=Mp)
@@ -501,83 +640,37 @@ class MIGTTrainer:
         else:
             dyp = ops.pack(dy, M, N, 1, sk=N, sn=1, st=0)                            # rows >= M are zero-filled by the packer
             ops.igemm(xt, dyp, K, Mp, N, gw, res=gw, lda=Mp)                         # dW += X^T dY
-        if not need_dx:
-            return None
-        return self._linear_dx(name, dy, M, res, dx_bf16, gelu_bwd_u, u_is_derivative)
 
-    serial_wgrad_split_as_overlapped = False
-    overlap_weight_gradients = True   # bf16 arm: the TN weight-gradient GEMM of a layer on a second stream beside that layer's dX GEMM
-    early_optimizer = False           # (measured in round 6: 19.660 vs 19.665 ms per step — the update hides, and the backward beside it slows by as much: off)
-                                      # bf16 arm: a layer's AdamWeightDecay update and the re-packing of its weights are issued on a third stream as soon as
-                                      # that layer's gradients are final (its backward and weight-gradient GEMMs done, its all-reduce complete) — HBM-bound
-                                      # work beside the matrix-bound backward of the layers below instead of 0.65 ms at the end of the step.  Same kernels on
-                                      # the same values: the parameters after a step are bit-identical (tests/test_train.py)
-    fused_optimizer_repack = True     # bf16 arm: the optimizer step writes the dense layers' bf16 packings from the updated weights in the same pass
-                                      # (vf_adamw_flat_pack_f32) instead of a re-pack launch that reads every weight again twice; bit-identical
-    _adam_pack = None
-    _packs_fresh = False
-    _opt_stream_obj = None
-    _layer_pack_ranges = None
-    _early_layers_done = False
-    _layer_nodecay = None
-    _head_nodecay = None
+    def _stream(self, name):
+        """the trainer's own HIP streams, created on first use: 'side' (weight-gradient GEMMs beside the dX GEMMs), 'opt' (early_optimizer)"""
+        if name not in self._streams:
+            self._streams[name] = torch.cuda.Stream(self.dev)
+        return self._streams[name]
 
-    def _opt_stream(self):
-        if self._opt_stream_obj is None:
-            self._opt_stream_obj = torch.cuda.Stream(self.dev)
-        return self._opt_stream_obj
+    def _join_side(self):
+        """the compute stream waits for the weight-gradient stream (before a layer's gradients are reduced, clipped or applied)"""
+        if self._side_busy:
+            torch.cuda.current_stream(self.dev).wait_stream(self._stream('side'))
+            self._side_busy = False
 
     def _adam_scalars(self):
-        c, step = self.cfg, self.step_count
+        step = self.step_count
         lr = learning_rate(step, self.lr_init, self.lr_total_steps, self.warmup_steps, self.lr_offset)
         t = step + 1
         return lr, lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
 
     def _early_update_layer(self, i, handle=None):
         """AdamWeightDecay over layer i's range of the flat buffer + its eight bf16 packings, on the optimizer stream"""
-        c = self.cfg
-        if self._layer_nodecay is None:                                      # (built on the main stream, before the optimizer stream's wait below)
-            self._layer_nodecay = []
-            for a, b in self.layer_ranges:
-                r = [[self.slices[n][0] - a, self.slices[n][1] - a] for n in self.names if 'bias' in n and a <= self.slices[n][0] < b]
-                self._layer_nodecay.append(torch.tensor(sorted(r), dtype=torch.int64, device=self.dev).reshape(-1, 2))
-        main, opt = torch.cuda.current_stream(self.dev), self._opt_stream()
+        args = self._adamw_args(*self.layer_ranges[i])                       # (the no-decay table is built on the main stream, before the wait below)
+        main, opt = torch.cuda.current_stream(self.dev), self._stream('opt')
         opt.wait_stream(main)                                                # the layer's backward (LayerNorm / bias gradients) is queued on main
         if self._side_busy:
-            opt.wait_stream(self._side_stream)                               # ... and its weight-gradient GEMMs + slab sums on the side stream
-        a, b = self.layer_ranges[i]
-        lr, lr_adam = self._adam_scalars()
+            opt.wait_stream(self._stream('side'))                            # ... and its weight-gradient GEMMs + slab sums on the side stream
         with torch.cuda.stream(opt):
             if handle is not None:
                 handle.wait()                                                # the layer's gradient all-reduce (this stream waits, not main)
-            T.adamw_flat_(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b],
-                          self._layer_nodecay[i] if c.weight_decay > 0 else None, lr * c.weight_decay if c.weight_decay > 0 else 0.0, lr_adam,
-                          self.b1, self.b2, self.eps)
+            T.adamw_flat_(*args)
             self._pack16(*self._layer_pack_ranges[i])
-
-    overlap_attention_backward = False  # bf16 arm: the attention backward's dK / dV launch on a third stream beside its dQ launch — same bits, measured
-                                        # 19.75 vs 19.65 ms per step (6 alternating rounds, round 6): the two kernels' workgroups sharing CUs cost more
-                                        # than their tails; off
-    _kv_stream_obj = None
-
-    def _kv_stream(self):
-        if self._kv_stream_obj is None:
-            self._kv_stream_obj = torch.cuda.Stream(self.dev)
-        return self._kv_stream_obj
-
-    _side_stream = None
-    _side_busy = False
-
-    def _side(self):
-        if self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(self.dev)
-        return self._side_stream
-
-    def _join_side(self):
-        """the compute stream waits for the weight-gradient stream (before a layer's gradients are reduced, clipped or applied)"""
-        if self._side_busy:
-            torch.cuda.current_stream(self.dev).wait_stream(self._side_stream)
-            self._side_busy = False
 
     def _linear_dx(self, name, dy, M, res=None, dx_bf16=False, gelu_bwd_u=None, u_is_derivative=False):
         """dx = dy @ W^T (+ res).  ``gelu_bwd_u`` (bf16 arm): the saved pre-activation u of the GELU that produced this layer's input —
@@ -606,16 +699,6 @@ class MIGTTrainer:
                 wpT = ops.pack(dn.w_raw, dn.n, dn.k, 1, sk=1, sn=dn.n, st=0)
             ops.igemm(dy, wpT, M, N, K, dx, res=res)
         return dx
-
-    prune_last_block = True           # the last block's projection / LayerNorm / MLP (forward and backward) and ln_f on the branch streams' rows only: the main
-                                      # stream's rows of the last block reach no loss (see train_step); its dropout masks there are indexed by the gathered rows
-    lazy_gradient_zero = True         # the transformer layers' gradient tensors (85 M of the 88 M) are not zero-filled at the start of a step: each is written
-                                      # exactly once per step, so its first writer STORES (sum_slabs / LayerNorm backward with accumulate off) instead of adding
-                                      # to a zero — one 337 MB fill and one 337 MB read of zeros less per step.  Keys still unset when a layer's (or the
-                                      # step's) backward ends are zero-filled then, so a tensor no kernel wrote is a zero gradient, as before.  The head range
-                                      # (embeddings, pose heads, ln_f: several contributions each) is zero-filled as before.  Same bits: x + 0 == x.
-    _unset = frozenset()
-    _layer_grad_keys = None
 
     def _begin_gradients(self):
         if not (self.lazy_gradient_zero and self.layer_ranges):
@@ -649,46 +732,18 @@ class MIGTTrainer:
             self._unset.discard(k)
 
     def _ln_bwd(self, name, dy, x, M, res=None, also_bf16=False, drop=(0.0, 0, 0)):
+        """-> (dx, its bf16 copy under ``drop``'s mask or None)"""
         d = self.cfg.d_model
-        return T.layernorm_bwd(dy, x, self.p(name + '.gamma'), self.g(name + '.gamma'), self.g(name + '.beta'), M, d, accumulate=not self._first_write(name),
-                               res=res, also_bf16=also_bf16, drop=drop if also_bf16 else (0.0, 0, 0))
+        dx = T.layernorm_bwd(dy, x, self.p(name + '.gamma'), self.g(name + '.gamma'), self.g(name + '.beta'), M, d, accumulate=not self._first_write(name),
+                             res=res, also_bf16=also_bf16, drop=drop if also_bf16 else (0.0, 0, 0))
+        return dx if also_bf16 else (dx, None)
 
-    bf16_preactivation = True         # bf16 arm, with both GELU fusions: c_fc's pre-activation u is SAVED as bf16 (the reference's mixed_float16 policy
-                                      # keeps every activation in half precision); gelu(u) is still taken from the fp32 accumulator, gelu'(u)
-                                      # in the backward epilogue from the rounded u.  False: u saved as fp32.
-    save_gelu_derivative = True       # bf16 arm, with bf16_preactivation: what c_fc saves for the backward is gelu'(u) (bf16, from the erf / exp evaluation its GELU
-                                      # makes anyway: three more instructions per element) instead of u, whose only reader — the GELU-backward epilogue of the
-                                      # mlp.c_proj dX GEMM — then multiplies by a loaded value instead of evaluating erf + exp per element again (that epilogue
-                                      # was 22 us of a 148 us launch).  gelu' is taken from the fp32 pre-activation and rounded once; before it was evaluated
-                                      # on the bf16-rounded u
-    fuse_gelu_forward = True          # bf16 arm: c_fc writes u (fp32, saved) and bf16 gelu(u) from one epilogue (VF_EPI_GELU_DUAL); the GELU there
-                                      # is the inference arm's vf_gelu_erf_fast (|err| 1.5e-7: a few outputs round to the neighbouring bf16)
-
-    bf16_residual_gradient = True     # bf16 arm: the LayerNorm backward also writes its result as bf16 — the operand of the two projection
-                                      # layers' backward GEMMs, which then run on the 256-tile kernel (the rounding is the one the GEMM's operand
-                                      # load applied anyway; only the two bias gradients see it)
-
-    small_n_pose_head = True          # the pose head's 1536 -> 7 layer and its dW on the one-pass small-N kernels (False: the implicit-GEMM kernel, round 5)
-    bf16_lm_head = True               # bf16 arm: the tied LM head (logits, dH, dwte) on the bf16 pipe like every other wide layer (the native-f32
-                                      # GEMMs it replaces were 0.8 ms of a 21 ms step); False: native f32 MFMA
-    _lm16 = None
-    _lm_T_stale = True
-    one_launch_repack = True          # bf16 arm: all weight packings refreshed by one launch per step
-    _pack16 = None
-    _pack16_keep = None
-    fuse_gelu_backward = True         # bf16 arm: d(pre-activation) = dX(mlp.c_proj) * gelu'(u) in that GEMM's epilogue (same bits as the two passes)
-    bf16_gradient_operands = True     # bf16 arm: gelu_bwd / attention backward write their gradients as bf16 (see train_step)
-    tn_weight_gradient = True         # bf16 arm: dW / db of the wide layers straight from the row-major operands (False: transpose + pack + column sums)
-    bf16_saved_activations = True     # bf16 arm: LayerNorm outputs / MLP hidden saved as bf16 (see train_step); False keeps them fp32 (same gradients)
-    attention_arith = 'bf16'          # bf16 arm only: 'bf16' = attention forward / backward on the bf16 matrix pipe; 'f32' = the exact-f32 kernels
-    fused_optimizer = True            # AdamWeightDecay as ONE launch over the flat buffer (False: one launch per tensor, 468 per step; bit-identical)
-    _nodecay = None
-    attention_backward = 'flash'      # 'dense': the first version (P materialised per head with batched GEMMs), kept for A/B
-
-    scene_offset = None               # index of this rank's first scene in the GLOBAL batch of a data-parallel step (None: rank * local batch).
-                                      # Every random draw of the step — the dropout masks, the random pose multiplier — is a function of
-                                      # the GLOBAL scene index, so N ranks draw exactly what one process draws on the concatenated batch,
-                                      # and no two replicas share a mask (with one seed per step and local indices they all would)
+    @staticmethod
+    def _proj_dy(st, g, g16, drop):
+        """the dY of a projection layer whose output went through the dropout site ``drop``, from the residual-stream gradient ``g``: with
+        dropout that gradient under the layer's OUTPUT mask — the bf16 copy the LayerNorm backward masked while it wrote it (the fp32 gradient
+        stays unmasked), or a dropout_add pass — otherwise the gradient itself"""
+        return g16 if st.plan.res16 else T.dropout_add(g, *drop[:3], row0=drop[3]) if drop[0] else g
 
     def _scene_offset(self, B):
         if self.scene_offset is not None:
@@ -705,20 +760,19 @@ class MIGTTrainer:
         """per-step dropout seed (uint32) from ``dropout_seed`` and the step counter"""
         return (int(self.dropout_seed) * 0x9E3779B1 + int(step) * 0x85EBCA77 + 0x1234567) & 0xFFFFFFFF
 
-    def _attn_bwd(self, qkv, datt, B, Tn, L, spec, att=None, lse=None, drop=(0.0, 0, 0)):
-        """dQKV from dA (branching_attention.py:82-126 semantics).  'flash': one pair of kernels per layer re-materialises the
-        probabilities tile by tile from the saved log-sum-exp and skips masked tiles; 'dense': per head with batched GEMMs."""
-        c = self.cfg
-        d, H = c.d_model, c.n_head
-        M = B * Tn
-        dqkv = torch.empty((M, 3 * d), dtype=torch.float32, device=qkv.device)
-        if drop[0] and not (self.attention_backward == 'flash' and att is not None and lse is not None):
+    def _attn_bwd(self, qkv, datt, st, att, lse, drop):
+        """dQKV from dA (branching_attention.py:82-126 semantics) with the STREAMS mask.  The bf16 kernels where the plan has them; else
+        'flash': one pair of kernels per layer re-materialises the probabilities tile by tile from the saved log-sum-exp and skips masked
+        tiles; 'dense': per head with batched GEMMs."""
+        d, H = self.cfg.d_model, self.cfg.n_head
+        B, Tn, L, spec, attn16 = st.B, st.Tn, st.L, -st.S, st.plan.attn16
+        dqkv = torch.empty((st.M, 3 * d), dtype=torch.bfloat16 if attn16 and st.plan.grad16 else torch.float32, device=qkv.device)
+        flash = attn16 or self.attention_backward == 'flash'
+        if drop[0] and not flash:
             raise NotImplementedError("attention dropout needs attention_backward='flash'")
-        if self.attention_backward == 'flash' and att is not None and lse is not None:
-            # thirds are (V, Q, K) (migt.py:207-213): gradients land in the same thirds of dqkv
-            T.attn_bwd(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], att, datt, lse,
-                       dqkv[:, d:2 * d], dqkv[:, 2 * d:], dqkv[:, :d], B, H, Tn, L,
-                       3 * d, 3 * d, 3 * d, d, d, 3 * d, 3 * d, 3 * d, 1.0, spec, drop=drop)
+        if flash:
+            thirds, ld = qkv_thirds(qkv, d)
+            (T.attn_bwd_bf16 if attn16 else T.attn_bwd)(*thirds, att, datt, lse, *qkv_thirds(dqkv, d)[0], B, H, Tn, L, *ld, d, d, *ld, 1.0, spec, drop=drop)
             return dqkv
         S = torch.empty((B, Tn, Tn), dtype=torch.float32, device=qkv.device)
         dP = torch.empty_like(S)
@@ -748,8 +802,6 @@ class MIGTTrainer:
         return dqkv
 
     # ------------------------------------------------------------------ the step
-    last_plan = None                  # the StepPlan of the last train_step call
-
     def plan(self, B, S, L, NS, rate=0.0, row0=0):
         """step_plan with this trainer's config, precision and switches"""
         return step_plan(self.cfg, self.model.precision, B, S, L, NS, rate, row0, **{k: getattr(self, k) for k in PLAN_SWITCHES})
@@ -759,33 +811,67 @@ class MIGTTrainer:
         Returns the metrics dict of MIGT.train_step (loss, ce_loss, acc, pose_* ...).  ``_forward_only`` (test_step / predict_step):
         the same multi-stream graph with ``training=False`` — no dropout, no random pose multiplier — up to the losses; returns
         ``(metrics, outputs)``."""
-        m, c, dev = self.model, self.cfg, self.dev
-        poses = poses.to(dev)
-        tokens = tokens.to(dev)
+        poses, tokens = poses.to(self.dev), tokens.to(self.dev)
+        st = self._begin_step(poses, tokens, training=not _forward_only)
+        # ---- forward with saved activations
+        h, emb = self._embed_forward(st, poses, tokens)
+        saved = []
+        for i in range(self.cfg.n_layer):
+            h, rec = self._block_forward(i, h, st)
+            if st.training:
+                saved.append(rec)
+        metrics, outputs, heads = self._losses(st, h, poses, emb)
+        if not st.training:
+            return metrics, outputs
+        # ---- backward; a layer's gradients are reduced (and with early_optimizer applied) as soon as they are final
+        overlap, early = self._overlap_plan(reduce_gradients, apply_update)
+        dh, dh16 = self._heads_backward(st, h, heads)
+        handles = []
+        for i in reversed(range(self.cfg.n_layer)):
+            dh, dh16 = self._block_backward(i, saved[i], dh, dh16, st)
+            saved[i] = None
+            hd = None
+            if overlap:
+                self._join_side()
+                hd = self._allreduce_range(*self.layer_ranges[i])
+                handles.append(hd)
+            if early:
+                self._early_update_layer(i, hd[0] if hd is not None else None)
+        self._embed_backward(st, dh, emb)
+        # ---- clip (per replica, per tensor, before aggregation), all-reduce SUM, AdamWeightDecay
+        self._finish_gradients(reduce_gradients, apply_update, overlap, early, handles)
+        return metrics
+
+    def _begin_step(self, poses, tokens, training):
+        """check the batch, decide the step's arms (step_plan: the bf16 arm's fast paths and the pruned last block, one decision from the shapes,
+        valid at every row count it is used at), zero what the gradients need zeroed -> the step's record"""
+        c = self.cfg
         if poses.dtype != torch.float32:
             raise TypeError('poses must be float32 (migt.py:346)')
         B, S = tokens.shape[:2]
         L = int(np.prod(tokens.shape[2:]))
-        d, H, nE = c.d_model, c.n_head, c.n_embeddings
-        use_loc = m.use_localization
-        NS = 3 if use_loc else 2
-        V = NS * S
-        Tn, M, M1 = V * L, B * V * L, B * S * L
-        skip = c.n_loss_skip
-        if not 0 <= skip < S:
+        NS = 3 if self.model.use_localization else 2
+        if not 0 <= c.n_loss_skip < S:
             raise ValueError('n_loss_skip must be < sequence length')
         if S < 2:
             raise ValueError('train_step needs sequences of at least 2 views (the STREAMS attention mask encodes the stream '
                              'length as -S <= -2; a 1-view sequence has nothing to condition on)')
-        if not _forward_only:
+        if training:
             self._begin_gradients()
+        rate = float(c.dropout) if training else 0.0
+        b0 = self._scene_offset(B) if rate else 0
+        plan = self.last_plan = self.plan(B, S, L, NS, rate, b0 * NS * S * L)
+        return Step(B=B, S=S, L=L, NS=NS, V=NS * S, Tn=NS * S * L, M=plan.M, M1=B * S * L, Mx=plan.Mx, rate=rate, seed=self.step_seed(self.step_count),
+                    row0=b0 * NS * S * L, plane0=b0 * c.n_head, plan=plan, training=training)
 
-        # ---- forward with saved activations --------------------------------------------------------------
-        seed = self.step_seed(self.step_count)
+    def _embed_forward(self, st, poses, tokens):
+        """the pose embedding MLP and the streams' embeddings (migt.py:392-403) -> (h [M][d], EmbedSaved)"""
+        m, c, dev = self.model, self.cfg, self.dev
+        B, S, L, d = st.B, st.S, st.L, c.d_model
         rmul = None
         pin = geometry.pose_model_input(poses, c.pose_multiplier)
-        if c.random_pose_multiplier != 1 and not _forward_only:                      # migt.py:350-354: rpm ** U(-1, 1) per scene (training only)
-            rmul = self.random_pose_factors(B, seed, self._scene_offset(B)).to(dev)
+        if c.random_pose_multiplier != 1 and st.training:                            # migt.py:350-354: rpm ** U(-1, 1) per scene (training only)
+            rmul = self.random_pose_factors(B, st.seed, self._scene_offset(B)).to(dev)
             pin = torch.cat([pin[..., :3] * rmul.view(B, 1, 1), pin[..., 3:]], -1)
         pin = pin.reshape(B * S, 7).contiguous()
         fc = m._dense['pose_embedding.c_fc']
@@ -793,78 +879,61 @@ class MIGTTrainer:
         h1 = T.gelu(u1)
         pe = self._linear(h1, 'pose_embedding.c_proj', B * S).view(B, S, d)
         tok = tokens.reshape(B, S, L)
-        ids_streams = [tok, torch.full_like(tok, m.mask_token)]
-        add_streams = [pe, pe]
-        if use_loc:
-            ids_streams.append(tok)
-            add_streams.append(m._wte[m.localization_token].view(1, 1, d).expand(B, S, d))
-        ids32 = torch.cat(ids_streams, 1).reshape(M).to(torch.int32).contiguous()
-        add = torch.cat(add_streams, 1).contiguous().view(B * V, d)
-        h = ops.embed_sum(ids32, m._wte, m._wpe, add, B * V, L, d, nE + 2)
-        rate = 0.0 if _forward_only else float(c.dropout)                            # Dropout layers are inert with training=False
-        b0 = self._scene_offset(B) if rate else 0
-        row0, plane0 = b0 * V * L, b0 * H                                            # this rank's first row / first attention plane in the global batch
-        if rate:
-            T.dropout_add(h, rate, seed, SITE_EMBED, out=h, row0=row0)               # self.drop, migt.py:403
-        saved = []
-        # the bf16 arm's fast paths and the pruned last block: one decision from the shapes, valid at every row count it is used at (step_plan)
-        plan = self.plan(B, S, L, NS, rate, row0)
-        self.last_plan = plan
-        attn16, act16, grad16, res16 = plan.attn16, plan.act16, plan.grad16, plan.res16
-        drop_of = lambda site: (rate, seed, site, row0)                              # noqa: E731  (elementwise sites: row offset)
-        drop_attn = lambda i_: (rate, seed, site_attn(i_), plane0)                   # noqa: E731  (attention: plane offset)
-        # prune_last_block: the losses read the branch streams only (MASK -> LM head, LOC -> pose head: migt.py:416-448); every block but the last needs
-        # the main stream's rows as keys and values of the next one, the LAST block's projection / LayerNorm / MLP on them feed nothing — and their
-        # backward multiplies zeros.  From the last block's attention on, forward and backward run on the NS - 1 branch streams' rows (gathered:
-        # they are contiguous per scene), ln_f with them; the attention backward and everything below it get the two gradients scattered back with
-        # zeros in the main stream's rows, which is what they were.  The dropout masks of the last block's two sites are indexed by the gathered rows
-        nb = NS - 1
-        tail, Mx = plan.tail, plan.Mx                                                # Mx: rows from the last block's projection on
-        drop_x = (lambda site: (rate, seed, site, row0 // NS * nb)) if tail else drop_of      # noqa: E731
-        for i in range(c.n_layer):
-            p = f'h.{i}'
-            n1 = ops.layernorm(h, *m._ln[p + '.ln_1'], M, d, out_bf16=act16)
-            if attn16:
-                # bf16 arm: c_attn writes q | k | v as bf16, the LDS-DMA kernel of the inference arm (+ log-sum-exp) writes a bf16 output
-                # that c_proj reads as it is (the rounding the GEMM would apply on load)
-                qkv = m._gemm(n1, p + '.attn.c_attn', M, out_bf16=True)
-                att = torch.empty((M, d), dtype=torch.bfloat16, device=dev)
-                lse = T.attn_fwd_lse_bf16(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], att, B, H, Tn, L, 3 * d, 3 * d, 3 * d, d, 1.0, -S,
-                                          drop=drop_attn(i))
-            else:
-                qkv = self._linear(n1, p + '.attn.c_attn', M)
-                att = torch.empty((M, d), dtype=torch.float32, device=dev)
-                lse = T.attn_fwd_lse(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], att, B, H, Tn, L, 3 * d, 3 * d, 3 * d, d, 1.0, -S,
-                                     drop=drop_attn(i))
-            last = tail and i == c.n_layer - 1
-            Mi, drop_i = (Mx, drop_x) if last else (M, drop_of)
-            att_i, h_i = att, h
-            if last:
-                att_i = att.view(B, NS, S * L, att.shape[-1])[:, 1:].reshape(Mx, att.shape[-1])
-                h_i = h.view(B, NS, S * L, d)[:, 1:].reshape(Mx, d)
-            h_mid = self._proj_dropout(att_i, p + '.attn.c_proj', Mi, h_i, drop_i(site_resid(i)), plan.drop16)    # h + resid_dropout(c_proj(a)), migt.py:216,233
-            n2 = ops.layernorm(h_mid, *m._ln[p + '.ln_2'], Mi, d, out_bf16=act16)
-            if plan.gelu_dual_x if last else plan.gelu_dual:
-                # c_fc keeps the pre-activation for the backward pass AND hands bf16 gelu(u) to mlp.c_proj from one epilogue
-                dn = m._dense[p + '.mlp.c_fc']
-                u16 = plan.u16
-                u = torch.empty((Mi, dn.n), dtype=torch.bfloat16 if u16 else torch.float32, device=dev)
-                f = torch.empty((Mi, dn.n), dtype=torch.bfloat16, device=dev)
-                u_deriv = plan.gelu_derivative                                            # (`u` then holds gelu'(u): see save_gelu_derivative)
-                ops.igemm(n2, dn.wp16, Mi, dn.k, dn.n, u, bias=dn.bias, epilogue=ops.EPI_GELU_DUAL, bf16=True, a16=True, o16=u16, out_aux=f,
-                          gelu_grad=u_deriv)
-            else:
-                u_deriv = False
-                u = self._linear(n2, p + '.mlp.c_fc', Mi)
-                f = T.gelu(u, out_bf16=act16)
-            h_out = self._proj_dropout(f, p + '.mlp.c_proj', Mi, h_mid, drop_i(site_mlp(i)), plan.drop16)         # h + dropout(mlp(...)), migt.py:72,237
-            if not _forward_only:
-                saved.append((h, n1, qkv, att, att_i, h_mid, n2, u, f, lse, u_deriv))
-            h = h_out
-        so = 1 if tail else 0                                                         # (hf's first stream: the main stream is not there when pruned)
-        hf = ops.layernorm(h, *m._ln['ln_f'], Mx, d).view(B, NS - so, S, L, d)
+        streams = [(tok, pe), (torch.full_like(tok, m.mask_token), pe)]              # (ids, additive embedding) of the main and the MASK stream
+        if st.NS == 3:                                                               # ... and the LOC stream
+            streams.append((tok, m._wte[m.localization_token].view(1, 1, d).expand(B, S, d)))
+        ids32 = torch.cat([ids for ids, _ in streams], 1).reshape(st.M).to(torch.int32).contiguous()
+        add = torch.cat([a for _, a in streams], 1).contiguous().view(B * st.V, d)
+        h = ops.embed_sum(ids32, m._wte, m._wpe, add, B * st.V, L, d, c.n_embeddings + 2)
+        if st.rate:
+            T.dropout_add(h, st.rate, st.seed, SITE_EMBED, out=h, row0=st.row0)      # self.drop, migt.py:403
+        return h, EmbedSaved(pin, u1, h1, ids32, tok, rmul)
 
-        # ---- losses (migt.py:416-448) ---------------------------------------------------------------------
+    def _block_rows(self, i, st):
+        """(pruned?, rows, elementwise dropout tuples) of block i from its projection on.  prune_last_block: the losses read the branch streams
+        only (MASK -> LM head, LOC -> pose head: migt.py:416-448); every block but the last needs the main stream's rows as keys and values of
+        the next one, the LAST block's projection / LayerNorm / MLP on them feed nothing — and their backward multiplies zeros.  From the last
+        block's attention on, forward and backward run on the NS - 1 branch streams' rows (Step.branch_rows), ln_f with them; the attention
+        backward and everything below it get the two gradients scattered back with zeros in the main stream's rows, which is what they were."""
+        last = st.plan.tail and i == self.cfg.n_layer - 1
+        return (True, st.Mx, st.drop_branch) if last else (False, st.M, st.drop)
+
+    def _block_forward(self, i, h, st):
+        """transformer block i on the residual stream h -> (the stream after it, BlockSaved)"""
+        m, d, H, dev, plan, p = self.model, self.cfg.d_model, self.cfg.n_head, self.dev, st.plan, f'h.{i}'
+        n1 = ops.layernorm(h, *m._ln[p + '.ln_1'], st.M, d, out_bf16=plan.act16)
+        # bf16 arm: c_attn writes q | k | v as bf16, the LDS-DMA kernel of the inference arm (+ log-sum-exp) writes a bf16 output that c_proj
+        # reads as it is (the rounding the GEMM would apply on load); otherwise the exact-f32 kernel.  Attention dropout is inside both
+        qkv = m._gemm(n1, p + '.attn.c_attn', st.M, out_bf16=True) if plan.attn16 else self._linear(n1, p + '.attn.c_attn', st.M)
+        att = torch.empty((st.M, d), dtype=qkv.dtype, device=dev)
+        thirds, ld = qkv_thirds(qkv, d)
+        lse = (T.attn_fwd_lse_bf16 if plan.attn16 else T.attn_fwd_lse)(*thirds, att, st.B, H, st.Tn, st.L, *ld, d, 1.0, -st.S, drop=st.drop_attn(i))
+        last, Mi, drop_i = self._block_rows(i, st)
+        att_i, h_i = (st.branch_rows(att), st.branch_rows(h)) if last else (att, h)
+        h_mid = self._proj_dropout(att_i, p + '.attn.c_proj', Mi, h_i, drop_i(site_resid(i)), plan.drop16)    # h + resid_dropout(c_proj(a)), migt.py:216,233
+        n2 = ops.layernorm(h_mid, *m._ln[p + '.ln_2'], Mi, d, out_bf16=plan.act16)
+        u_deriv = False
+        if plan.gelu_dual_x if last else plan.gelu_dual:
+            # c_fc keeps the pre-activation for the backward pass AND hands bf16 gelu(u) to mlp.c_proj from one epilogue
+            dn = m._dense[p + '.mlp.c_fc']
+            u = torch.empty((Mi, dn.n), dtype=torch.bfloat16 if plan.u16 else torch.float32, device=dev)
+            f = torch.empty((Mi, dn.n), dtype=torch.bfloat16, device=dev)
+            u_deriv = plan.gelu_derivative                                            # (`u` then holds gelu'(u): see save_gelu_derivative)
+            ops.igemm(n2, dn.wp16, Mi, dn.k, dn.n, u, bias=dn.bias, epilogue=ops.EPI_GELU_DUAL, bf16=True, a16=True, o16=plan.u16, out_aux=f,
+                      gelu_grad=u_deriv)
+        else:
+            u = self._linear(n2, p + '.mlp.c_fc', Mi)
+            f = T.gelu(u, out_bf16=plan.act16)
+        h_out = self._proj_dropout(f, p + '.mlp.c_proj', Mi, h_mid, drop_i(site_mlp(i)), plan.drop16)         # h + dropout(mlp(...)), migt.py:72,237
+        return h_out, BlockSaved(h, n1, qkv, att, att_i, h_mid, n2, u, f, lse, u_deriv)
+
+    def _losses(self, st, h, poses, emb):
+        """ln_f, the token cross-entropy on the MASK stream, the pose MSE on the LOC stream (migt.py:416-448) -> (metrics, the outputs of a
+        forward-only step or None, HeadsSaved)"""
+        m, c, dev = self.model, self.cfg, self.dev
+        B, S, L, M1, d, nE, skip, tok = st.B, st.S, st.L, st.M1, c.d_model, c.n_embeddings, c.n_loss_skip, emb.tok
+        so = 1 if st.plan.tail else 0                                                 # (hf's first stream: the main stream is not there when pruned)
+        hf = ops.layernorm(h, *m._ln['ln_f'], st.Mx, d).view(B, st.NS - so, S, L, d)
         view_ok = (torch.arange(S, device=dev) >= skip).float().view(1, S, 1).expand(B, S, L).reshape(M1)
         denom = float((S - skip) * L * B)
         hmask = hf[:, 1 - so].contiguous().view(M1, d)
@@ -882,61 +951,72 @@ class MIGTTrainer:
         metrics = dict(ce_loss=ce_b.mean())
         pred = ops.argmax_rows(logits, M1, nE).view(B, S, L)
         metrics['acc'] = (pred[:, skip:] == tok[:, skip:]).float().mean()
-        if use_loc:
-            loc_w = float(self.loc_weight(self.step_count))
-            hloc = hf[:, 2 - so].contiguous().view(M1, d)
-            up = self._linear(hloc, 'pose_criterion.pose_classifier.c_fc', M1)
-            p1 = T.gelu(up)
-            dn_p = m._dense['pose_criterion.pose_classifier.c_proj']
-            small_n = self.small_n_pose_head and T.dense_small_n_supported(dn_p.k, dn_p.n) and p1.dtype == torch.float32 and p1.is_contiguous()
-            if small_n:          # 1536 -> 7: one pass over p1 instead of an implicit GEMM on a 32-column tile (176 -> ~15 us, round 6)
-                raw = T.dense_small_n(p1, dn_p.w_raw, dn_p.bias, M1, dn_p.k, dn_p.n)
-            else:
-                raw = self._linear(p1, 'pose_criterion.pose_classifier.c_proj', M1)
-            dyn = c.use_dynamic_pose_loss
-            if dyn:                                                                  # DynamicLossWeightingCriterion, migt.py:107-120
-                sw = self.p(DYN_KEY)
-                e_pos, e_ori = float(torch.exp(-sw[0])), float(torch.exp(-sw[1]))
-                rows_per_scene = float((S - skip) * L)
-                w_pos = (view_ok * (loc_w * e_pos / rows_per_scene)).contiguous()    # reduce_SUM over the batch (:117): no 1/B
-                w_ori = (view_ok * (loc_w * e_ori / rows_per_scene)).contiguous()
-            else:
-                w_pos = w_ori = (view_ok * (loc_w / denom)).contiguous()
-            div = None if rmul is None else rmul.view(B, 1).expand(B, S * L).reshape(M1).contiguous()
-            pos_r, ori_r, draw = T.pose_mse(raw, poses.reshape(B * S, 7).contiguous(), w_pos, M1, L, c.pose_multiplier, w_ori=w_ori,
-                                            xyz_div=div)
-            pos_b = pos_r.view(B, S, L)[:, skip:].mean((1, 2))
-            ori_b = ori_r.view(B, S, L)[:, skip:].mean((1, 2))
-            if dyn:
-                pose_loss = (sw[0] + e_pos * pos_b + sw[1] + e_ori * ori_b).sum()    # a scalar, broadcast onto every scene (:440,447)
-                loss_b = loss_b + pose_loss * loc_w
-                gs = self.g(DYN_KEY)
-                gs[0] = loc_w * (B - e_pos * pos_b.sum())
-                gs[1] = loc_w * (B - e_ori * ori_b.sum())
-                metrics.update(dynamic_loss_weight_pos=sw[0].clone(), dynamic_loss_weight_ori=sw[1].clone(), pose_loss=pose_loss)
-            else:
-                loss_b = loss_b + (pos_b + ori_b) * loc_w
-                metrics['pose_loss'] = (pos_b + ori_b).mean()
-            metrics.update(pose_pos_loss=pos_b.mean(), pose_ori_loss=ori_b.mean(), localization_weight=loc_w)
+        raw = pose = None
+        if st.NS == 3:
+            pose_term, raw, pose = self._pose_loss(st, hf[:, 2 - so], view_ok, denom, poses, emb.rmul, metrics)
+            loss_b = loss_b + pose_term
         metrics['loss'] = loss_b.mean()                                              # reduce_mean, migt.py:476
-        if _forward_only:
-            return metrics, dict(logits=logits.view(B, S, L, nE), predicted_tokens=pred,
-                                 pose_head_raw=raw.view(B, S, L, 7) if use_loc else None)
+        outputs = None if st.training else dict(logits=logits.view(B, S, L, nE), predicted_tokens=pred,
+                                                pose_head_raw=raw.view(B, S, L, 7) if st.NS == 3 else None)
+        return metrics, outputs, HeadsSaved(hmask, dlogits, lm16, pose)
 
-        # ---- backward -------------------------------------------------------------------------------------
-        dhf = torch.zeros((B, NS - so, S, L, d), dtype=torch.float32, device=dev)
+    def _pose_loss(self, st, hloc, view_ok, denom, poses, rmul, metrics):
+        """the pose head on the LOC stream's rows ``hloc`` and its MSE (migt.py:432-448); adds its metrics -> (the term of the per-scene loss,
+        the head's raw output, PoseSaved)"""
+        m, c = self.model, self.cfg
+        B, S, L, M1, skip = st.B, st.S, st.L, st.M1, c.n_loss_skip
+        loc_w = float(self.loc_weight(self.step_count))
+        hloc = hloc.contiguous().view(M1, c.d_model)
+        up = self._linear(hloc, 'pose_criterion.pose_classifier.c_fc', M1)
+        p1 = T.gelu(up)
+        dn_p = m._dense['pose_criterion.pose_classifier.c_proj']
+        small_n = self.small_n_pose_head and T.dense_small_n_supported(dn_p.k, dn_p.n) and p1.dtype == torch.float32 and p1.is_contiguous()
+        if small_n:          # 1536 -> 7: one pass over p1 instead of an implicit GEMM on a 32-column tile (176 -> ~15 us, round 6)
+            raw = T.dense_small_n(p1, dn_p.w_raw, dn_p.bias, M1, dn_p.k, dn_p.n)
+        else:
+            raw = self._linear(p1, 'pose_criterion.pose_classifier.c_proj', M1)
+        dyn = c.use_dynamic_pose_loss
+        if dyn:                                                                  # DynamicLossWeightingCriterion, migt.py:107-120
+            sw = self.p(DYN_KEY)
+            e_pos, e_ori = float(torch.exp(-sw[0])), float(torch.exp(-sw[1]))
+            rows_per_scene = float((S - skip) * L)
+            w_pos = (view_ok * (loc_w * e_pos / rows_per_scene)).contiguous()    # reduce_SUM over the batch (:117): no 1/B
+            w_ori = (view_ok * (loc_w * e_ori / rows_per_scene)).contiguous()
+        else:
+            w_pos = w_ori = (view_ok * (loc_w / denom)).contiguous()
+        div = None if rmul is None else rmul.view(B, 1).expand(B, S * L).reshape(M1).contiguous()
+        pos_r, ori_r, draw = T.pose_mse(raw, poses.reshape(B * S, 7).contiguous(), w_pos, M1, L, c.pose_multiplier, w_ori=w_ori, xyz_div=div)
+        pos_b = pos_r.view(B, S, L)[:, skip:].mean((1, 2))
+        ori_b = ori_r.view(B, S, L)[:, skip:].mean((1, 2))
+        if dyn:
+            pose_loss = (sw[0] + e_pos * pos_b + sw[1] + e_ori * ori_b).sum()    # a scalar, broadcast onto every scene (:440,447)
+            gs = self.g(DYN_KEY)
+            gs[0] = loc_w * (B - e_pos * pos_b.sum())
+            gs[1] = loc_w * (B - e_ori * ori_b.sum())
+            metrics.update(dynamic_loss_weight_pos=sw[0].clone(), dynamic_loss_weight_ori=sw[1].clone(), pose_loss=pose_loss)
+        else:
+            pose_loss = pos_b + ori_b
+            metrics['pose_loss'] = (pos_b + ori_b).mean()
+        metrics.update(pose_pos_loss=pos_b.mean(), pose_ori_loss=ori_b.mean(), localization_weight=loc_w)
+        return pose_loss * loc_w, raw, PoseSaved(hloc, up, p1, small_n, draw)
+
+    def _heads_backward(self, st, h, heads):
+        """the LM head's and the pose head's backward, ln_f's -> the gradient of the last block's output (fp32, bf16 copy or None)"""
+        m, c, dev = self.model, self.cfg, self.dev
+        B, S, L, M1, d, nE = st.B, st.S, st.L, st.M1, c.d_model, c.n_embeddings
+        hmask, dlogits = heads.hmask, heads.dlogits
+        so = 1 if st.plan.tail else 0
+        dhf = torch.zeros((B, st.NS - so, S, L, d), dtype=torch.float32, device=dev)
         # tied LM head: dH = dlogits @ wte[:nE];  dwte[:nE] = dlogits^T @ H
         dhm = torch.empty((M1, d), dtype=torch.float32, device=dev)
         gwte = self.g('wte.weight')
-        if lm16:
+        if heads.lm16:
             ops.igemm(dlogits, self._lm16[1], M1, nE, d, dhm, bf16=True)
             # dwte[:nE] = dlogits^T @ H straight from the row-major operands (the TN kernel: x = dlogits as bf16, dy = H)
             ops.gemm_tn_bf16(dlogits.to(torch.bfloat16), hmask, M1, nE, d, gwte[:nE], None)
         else:
-            if getattr(self, 'lm_T', None) is None or self._lm_T_stale:               # (M1 % 64 != 0 in the bf16 arm: repack() skipped the native
-                self.lm_T = ops.pack(m._wte, nE, d, 1, sk=d, sn=1, st=0,              # transposed packing — build it from the CURRENT weights, every
-                                     out=getattr(self, 'lm_T', None))                 # step: a packing cached from step 1 would be silently stale)
-                self._lm_T_stale = False
+            if self._lm_T_stale:              # (M1 % 64 != 0 in the bf16 arm: repack() skipped the native transposed packing — build it from the
+                self._pack_lm_T()             # CURRENT weights, every step: a packing cached from step 1 would be silently stale)
             ops.igemm(dlogits, self.lm_T, M1, nE, d, dhm)
             M1p = (M1 + 31) // 32 * 32                                                # reduction length padded to the K stage (B * S * L = 48 at
             dlt = T.transpose(dlogits, M1, nE, ld_dst=M1p,                            # 16-token views and an odd B * S)
@@ -944,8 +1024,8 @@ class MIGTTrainer:
             hp = ops.pack(hmask, M1, d, 1, sk=d, sn=1, st=0)                          # rows >= M1 are zero-filled by the packer
             ops.igemm(dlt, hp, nE, M1p, d, gwte, lda=M1p)                             # rows [0, nE) of the (zeroed) grad
         dhf[:, 1 - so] = dhm.view(B, S, L, d)
-        if use_loc:
-            name = 'pose_criterion.pose_classifier.c_proj'
+        if heads.pose is not None:
+            name, (hloc, up, p1, small_n, draw) = 'pose_criterion.pose_classifier.c_proj', heads.pose
             dn = m._dense[name]
             T.colsum(draw, self.g(name + '.bias'), M1, 7, accumulate=True)
             if small_n:          # dW = p1^T @ draw straight from the row-major operands (no transpose, no packing)
@@ -959,78 +1039,63 @@ class MIGTTrainer:
             dup = T.gelu_bwd(up, dp1)
             dhl = self._linear_bwd('pose_criterion.pose_classifier.c_fc', hloc, dup, M1)
             dhf[:, 2 - so] = dhl.view(B, S, L, d)
-        # with dropout, the bf16 copy of a residual-stream gradient is the dY of the projection layer that consumes it, i.e. that gradient
-        # under the layer's OUTPUT mask: the LayerNorm backward applies it while it writes the copy (the fp32 gradient stays unmasked)
         nl = c.n_layer
-        dh = self._ln_bwd('ln_f', dhf.view(Mx, d), h, Mx, also_bf16=res16 and nl > 0, drop=drop_x(site_mlp(nl - 1)))
-        dh, dh16 = dh if (res16 and nl > 0) else (dh, None)
-        handles = []
-        overlap = reduce_gradients and self._world() > 1 and not (c.gradient_clip_val and c.gradient_clip_val > 0)
-        # early per-layer optimizer (see early_optimizer): needs the one-launch optimizer and re-pack tables, no clipping pass over the finished
-        # gradients, and — with more than one rank — the per-layer fp32 all-reduce whose handle the optimizer stream can wait for
-        early = (self.early_optimizer and apply_update and self.fused_optimizer and self._pack16 is not None and self._layer_pack_ranges is not None
-                 and not (c.gradient_clip_val and c.gradient_clip_val > 0)
-                 and (self._world() == 1 or not reduce_gradients or (overlap and self.grad_allreduce_dtype == 'f32')))
-        for i in reversed(range(c.n_layer)):
-            p = f'h.{i}'
-            h_in, n1, qkv, att, att_i, h_mid, n2, u, f, lse, u_deriv = saved[i]
-            last = tail and i == c.n_layer - 1
-            Mi, drop_i = (Mx, drop_x) if last else (M, drop_of)
-            dy_mlp = dh16 if res16 else (T.dropout_add(dh, rate, seed, site_mlp(i), row0=drop_i(0)[3]) if rate else dh)      # d(mlp.c_proj output)
-            if plan.gelu_bwd16:                                                      # GELU backward in the epilogue of the dX GEMM that feeds it
-                du = self._linear_bwd(p + '.mlp.c_proj', f, dy_mlp, Mi, dx_bf16=True, gelu_bwd_u=u, u_is_derivative=u_deriv)
-            else:
-                df = self._linear_bwd(p + '.mlp.c_proj', f, dy_mlp, Mi)
-                du = T.gelu_bwd(u, df, out_bf16=grad16)
-            dn2 = self._linear_bwd(p + '.mlp.c_fc', n2, du, Mi)
-            dh_mid = self._ln_bwd(p + '.ln_2', dn2, h_mid, Mi, res=dh, also_bf16=res16, drop=drop_i(site_resid(i)))  # (+ the residual branch's gradient)
-            dh_mid, dh_mid16 = dh_mid if res16 else (dh_mid, None)
-            datt = self._linear_bwd(p + '.attn.c_proj', att_i,
-                                    dh_mid16 if res16 else (T.dropout_add(dh_mid, rate, seed, site_resid(i), row0=drop_i(0)[3]) if rate else dh_mid), Mi,
-                                    dx_bf16=attn16)
-            if last:
-                # back to all rows for the attention backward and the block's first half: the main stream's rows of d(attention output) and of the
-                # residual-stream gradient are zeros (nothing downstream of them reached a loss)
-                full = torch.zeros((B, NS, S * L, datt.shape[-1]), dtype=datt.dtype, device=dev)
-                full[:, 1:] = datt.view(B, nb, S * L, datt.shape[-1])
-                datt = full.view(M, datt.shape[-1])
-                full = torch.zeros((B, NS, S * L, d), dtype=torch.float32, device=dev)
-                full[:, 1:] = dh_mid.view(B, nb, S * L, d)
-                dh_mid = full.view(M, d)
-            if attn16:
-                dqkv = torch.empty((M, 3 * d), dtype=torch.bfloat16 if grad16 else torch.float32, device=dev)
-                T.attn_bwd_bf16(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv[:, :d], att, datt, lse, dqkv[:, d:2 * d], dqkv[:, 2 * d:], dqkv[:, :d],
-                                B, H, Tn, L, 3 * d, 3 * d, 3 * d, d, d, 3 * d, 3 * d, 3 * d, 1.0, -S, drop=drop_attn(i),
-                                kv_stream=self._kv_stream() if self.overlap_attention_backward else None)
-            else:
-                dqkv = self._attn_bwd(qkv, datt, B, Tn, L, -S, att=att, lse=lse, drop=drop_attn(i))
-            dn1 = self._linear_bwd(p + '.attn.c_attn', n1, dqkv, M)
-            dh = self._ln_bwd(p + '.ln_1', dn1, h_in, M, res=dh_mid, also_bf16=res16 and i > 0, drop=drop_of(site_mlp(i - 1)))
-            dh, dh16 = dh if (res16 and i > 0) else (dh, None)
-            saved[i] = None
-            hd = None
-            self._flush_unset(p + '.')
-            if overlap:                                                              # this layer's grads are final
-                self._join_side()
-                hd = self._allreduce_range(*self.layer_ranges[i])
-                handles.append(hd)
-            if early:
-                self._early_update_layer(i, hd[0] if hd is not None else None)
-        # embeddings: dwte scatter, dwpe, d(add) -> pose embedding MLP / LOC token row
-        if rate:
-            T.dropout_add(dh, rate, seed, SITE_EMBED, out=dh, row0=row0)
-        dadd = T.embed_bwd(dh, ids32, gwte, self.g('wpe.embeddings'), B * V, L, d, nE + 2).view(B, V, d)
-        dpe = (dadd[:, :S] + dadd[:, S:2 * S]).contiguous().view(B * S, d)
-        if use_loc:
-            T.colsum(dadd[:, 2 * S:].contiguous().view(B * S, d), gwte[m.localization_token], B * S, d, accumulate=True)
-        dh1 = self._linear_bwd('pose_embedding.c_proj', h1, dpe, B * S)
-        du1 = T.gelu_bwd(u1, dh1)
-        T.dense_small_k_bwd(pin, du1, self.g('pose_embedding.c_fc.weight'), self.g('pose_embedding.c_fc.bias'), B * S, 7, fc.n)
+        return self._ln_bwd('ln_f', dhf.view(st.Mx, d), h, st.Mx, also_bf16=st.plan.res16 and nl > 0, drop=st.drop_branch(site_mlp(nl - 1)))
 
-        # ---- clip (per replica, per tensor, before aggregation), all-reduce SUM, AdamWeightDecay ------------
+    def _block_backward(self, i, rec, dh, dh16, st):
+        """block i's backward from the gradient of its output (fp32 ``dh``, with StepPlan.res16 its bf16 copy under mlp.c_proj's output mask)
+        -> the gradient of its input, the same pair for block i - 1"""
+        plan, p = st.plan, f'h.{i}'
+        last, Mi, drop_i = self._block_rows(i, st)
+        dy_mlp = self._proj_dy(st, dh, dh16, drop_i(site_mlp(i)))                    # d(mlp.c_proj output)
+        if plan.gelu_bwd16:                                                          # GELU backward in the epilogue of the dX GEMM that feeds it
+            du = self._linear_bwd(p + '.mlp.c_proj', rec.f, dy_mlp, Mi, dx_bf16=True, gelu_bwd_u=rec.u, u_is_derivative=rec.u_deriv)
+        else:
+            df = self._linear_bwd(p + '.mlp.c_proj', rec.f, dy_mlp, Mi)
+            du = T.gelu_bwd(rec.u, df, out_bf16=plan.grad16)
+        dn2 = self._linear_bwd(p + '.mlp.c_fc', rec.n2, du, Mi)
+        dh_mid, dh_mid16 = self._ln_bwd(p + '.ln_2', dn2, rec.h_mid, Mi, res=dh, also_bf16=plan.res16, drop=drop_i(site_resid(i)))   # (+ the residual branch's gradient)
+        datt = self._linear_bwd(p + '.attn.c_proj', rec.att_i, self._proj_dy(st, dh_mid, dh_mid16, drop_i(site_resid(i))), Mi, dx_bf16=plan.attn16)
+        if last:                             # back to all rows for the attention backward and the block's first half
+            datt, dh_mid = st.scatter_branch_rows(datt), st.scatter_branch_rows(dh_mid)
+        dqkv = self._attn_bwd(rec.qkv, datt, st, rec.att, rec.lse, st.drop_attn(i))
+        dn1 = self._linear_bwd(p + '.attn.c_attn', rec.n1, dqkv, st.M)
+        dh, dh16 = self._ln_bwd(p + '.ln_1', dn1, rec.h, st.M, res=dh_mid, also_bf16=plan.res16 and i > 0, drop=st.drop(site_mlp(i - 1)))
+        self._flush_unset(p + '.')
+        return dh, dh16
+
+    def _embed_backward(self, st, dh, emb):
+        """embeddings: dwte scatter, dwpe, d(add) -> pose embedding MLP / LOC token row"""
+        m, d = self.model, self.cfg.d_model
+        B, S, V, gwte = st.B, st.S, st.V, self.g('wte.weight')
+        if st.rate:
+            T.dropout_add(dh, st.rate, st.seed, SITE_EMBED, out=dh, row0=st.row0)
+        dadd = T.embed_bwd(dh, emb.ids32, gwte, self.g('wpe.embeddings'), B * V, st.L, d, self.cfg.n_embeddings + 2).view(B, V, d)
+        dpe = (dadd[:, :S] + dadd[:, S:2 * S]).contiguous().view(B * S, d)
+        if st.NS == 3:
+            T.colsum(dadd[:, 2 * S:].contiguous().view(B * S, d), gwte[m.localization_token], B * S, d, accumulate=True)
+        dh1 = self._linear_bwd('pose_embedding.c_proj', emb.h1, dpe, B * S)
+        du1 = T.gelu_bwd(emb.u1, dh1)
+        T.dense_small_k_bwd(emb.pin, du1, self.g('pose_embedding.c_fc.weight'), self.g('pose_embedding.c_fc.bias'), B * S, 7,
+                            m._dense['pose_embedding.c_fc'].n)
+
+    def _clipped(self):
+        return bool(self.cfg.gradient_clip_val and self.cfg.gradient_clip_val > 0)
+
+    def _overlap_plan(self, reduce_gradients, apply_update):
+        """(overlap, early): each layer's all-reduce issued as soon as its backward is done; the early per-layer optimizer (see
+        early_optimizer), which needs the one-launch optimizer and re-pack tables, no clipping pass over the finished gradients, and — with
+        more than one rank — the per-layer fp32 all-reduce whose handle the optimizer stream can wait for"""
+        overlap = reduce_gradients and self._world() > 1 and not self._clipped()
+        early = (self.early_optimizer and apply_update and self.fused_optimizer and self._pack16 is not None and self._layer_pack_ranges is not None
+                 and not self._clipped() and (self._world() == 1 or not reduce_gradients or (overlap and self.grad_allreduce_dtype == 'f32')))
+        return overlap, early
+
+    def _finish_gradients(self, reduce_gradients, apply_update, overlap, early, handles):
+        c = self.cfg
         self._flush_unset()
         self._join_side()
-        if c.gradient_clip_val and c.gradient_clip_val > 0:
+        if self._clipped():
             if self._scratch is None:
                 self._scratch = T.clip_scratch(self.flat_g.device)
             for n in self.names:
@@ -1057,14 +1122,7 @@ class MIGTTrainer:
         if apply_update:
             self.apply_gradients(layers_done=early)
             if early:
-                torch.cuda.current_stream(self.dev).wait_stream(self._opt_stream())     # the next forward reads the layers' new weights and packings
-        return metrics
-
-    grad_allreduce_dtype = 'f32'      # 'bf16': each range is all-reduced as a bf16 copy (177 MB instead of 354 MB on the links; the sum
-                                      # of the replicas' gradients is then rounded to 8 bits per replica term — an option, off by default:
-                                      # the reference's MirroredStrategy reduces fp32 variables' gradients in fp32)
-    time_allreduce = False            # record HIP events around the wait for the collectives (exposed_allreduce_ms())
-    _allreduce_events = None
+                torch.cuda.current_stream(self.dev).wait_stream(self._stream('opt'))     # the next forward reads the layers' new weights and packings
 
     def _allreduce_range(self, a, b):
         """async SUM all-reduce of flat_g[a:b] -> (handle, bf16 staging buffer or None, (a, b))"""
@@ -1127,39 +1185,24 @@ class MIGTTrainer:
         """``layers_done``: the transformer layers' ranges were already updated (and re-packed) by train_step's early per-layer optimizer: only the
         head range (embeddings, pose heads, ln_f) is left"""
         c = self.cfg
-        lr, lr_adam = self._adam_scalars()
         if self.fused_optimizer:
-            # one launch over the flat buffer; the "bias" tensors (models/utils.py:424: the only names excluded) as no-decay ranges
-            if self._nodecay is None:
-                r = [[self.slices[n][0], self.slices[n][1]] for n in self.names if 'bias' in n]
-                self._nodecay = torch.tensor(sorted(r), dtype=torch.int64, device=self.dev).reshape(-1, 2)
+            # one launch over the flat buffer (with the early optimizer: over the head range); the "bias" tensors as no-decay ranges
             if layers_done:
-                a, b = self.head_range
-                if self._head_nodecay is None:
-                    r = [[self.slices[n][0], self.slices[n][1]] for n in self.names if 'bias' in n and self.slices[n][0] < b]
-                    self._head_nodecay = torch.tensor(sorted(r), dtype=torch.int64, device=self.dev).reshape(-1, 2)
-                T.adamw_flat_(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b],
-                              self._head_nodecay if c.weight_decay > 0 else None, lr * c.weight_decay if c.weight_decay > 0 else 0.0, lr_adam,
-                              self.b1, self.b2, self.eps)
+                T.adamw_flat_(*self._adamw_args(*self.head_range))
             elif self.fused_optimizer_repack and self._adam_pack is not None and self._pack16 is not None:
-                T.adamw_flat_pack_(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self._nodecay if c.weight_decay > 0 else None,
-                                   lr * c.weight_decay if c.weight_decay > 0 else 0.0, lr_adam, self.b1, self.b2, self.eps, self._adam_pack)
+                T.adamw_flat_pack_(*self._adamw_args(), self._adam_pack)
                 self._packs_fresh = True
             else:
-                T.adamw_flat_(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self._nodecay if c.weight_decay > 0 else None,
-                              lr * c.weight_decay if c.weight_decay > 0 else 0.0, lr_adam, self.b1, self.b2, self.eps)
+                T.adamw_flat_(*self._adamw_args())
         else:
+            lr, lr_adam = self._adam_scalars()
             for n in self.names:
                 a, b, _ = self.slices[n]
                 decay = c.weight_decay > 0 and 'bias' not in n            # models/utils.py:424: only "bias" names are excluded
                 T.adamw_(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b],
                          lr * c.weight_decay if decay else 0.0, lr_adam, self.b1, self.b2, self.eps)
         self.step_count += 1
-        self._early_layers_done = bool(layers_done)
-        try:
-            self.repack()
-        finally:
-            self._early_layers_done = False
+        self.repack(early_layers_done=layers_done)
 
     def state_dict(self):
         return {n: self.p(n).detach().cpu().clone() for n in self.names}
