@@ -458,11 +458,11 @@ def test_full_size_codec_activations_stay_inside_the_variance_rule(dev, full_vq)
     frames, _ = synthetic_scene_batch(1, 4, 128, seed=int(g['input_seed']))
     layers, inner = [], m._gn
 
-    def spy(x, name, n, HW, Cc):
-        path = 'finalize' if m._stats_of is not None and m._stats_of[0] is x else 'stats'
+    def spy(x, name, n, HW, Cc, part=None):
+        path = 'finalize' if part is not None else 'stats'
         xg = x.double().view(n, HW, 32, Cc // 32)
         mean, var = xg.mean(dim=(1, 3)), xg.var(dim=(1, 3), unbiased=False)
-        out = inner(x, name, n, HW, Cc)
+        out = inner(x, name, n, HW, Cc, part)
         rstd = 1.0 / torch.sqrt(var + K.EPS)
         got = out[1].double().view(n, 32, Cc // 32) / m._norm[name][0].double().view(1, 32, Cc // 32)
         rel = (got - rstd.unsqueeze(-1)).abs() / rstd.unsqueeze(-1)

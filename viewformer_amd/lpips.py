@@ -101,16 +101,13 @@ class LPIPS:
     def _conv(x, w, bias, cache, n, H, W, activations=False):
         """``activations``: forward features (x3h applies); gradients stay on x6 (no range condition)"""
         cout, cin = w.shape[0], w.shape[1]
-        if ops.conv3_small_cout_supported(ops.MODE_CONV3_S1, cin, cout, H, W):
+        arm = ops.conv3_arm(ops.MODE_CONV3_S1, cin, cout, H, W, activations=activations)
+        if arm == 'small':
             return ops.conv3_small_cout(x, w, bias, n, H, W, cin, cout)
         out = torch.empty((n * H * W, cout), dtype=torch.float32, device=x.device)
-        x6 = ops.conv3_x6_supported(ops.MODE_CONV3_S1, cin, cout, H, W)
-        x3h = x6 and activations
-        key = 'x3h' if x3h else 'x6' if x6 else 'f32'
-        if key not in cache:
-            cache[key] = ops.pack_conv3_x3h(w) if x3h else ops.pack_conv3_x6(w) if x6 else ops.pack_conv_oihw(w)
-        ops.igemm(x, cache[key], n * H * W, cin, cout, out, bias=bias, mode=ops.MODE_CONV3_S1, Hin=H, Win=W, Hout=H, Wout=W,
-                  x6=x6 and not x3h, x3h=x3h)
+        if arm not in cache:
+            cache[arm] = ops.pack_conv3(arm, w)
+        ops.igemm(x, cache[arm], n * H * W, cin, cout, out, bias=bias, mode=ops.MODE_CONV3_S1, Hin=H, Win=W, Hout=H, Wout=W, **ops.ARM_KW[arm])
         return out
 
     def _features(self, img, n, H, W):

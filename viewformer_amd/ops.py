@@ -77,15 +77,41 @@ def pack_dense_nk(w, n_rows=None):
     return pack(w, k, n, 1, sk=1, sn=k, st=0)
 
 
+# one row per arm: the library's size and pack symbols, the packing's dtype, what the pack symbol takes behind the two strides
+_DENSE_PACK = {'bf16': ('vf_gemm_bf16_packed_elems', 'vf_gemm_bf16_pack', torch.bfloat16, (1, 0)),
+               'x6': ('vf_gemm_x6_packed_elems', 'vf_gemm_x6_pack', torch.bfloat16, ()),
+               'x3h': ('vf_gemm_x3h_packed_elems', 'vf_gemm_x3h_pack', torch.float16, ())}
+_CONV3_PACK = {'bf16': ('vf_conv3_bf16_packed_elems', 'vf_conv3_bf16_pack', torch.bfloat16),
+               'x6': ('vf_conv3_x6_packed_elems', 'vf_conv3_x6_pack', torch.bfloat16),
+               'x3h': ('vf_conv3_x3h_packed_elems', 'vf_conv3_x3h_pack', torch.float16)}
+
+
+def _pack_dense(arm, w, transposed, n_rows=None):
+    """w = [K][N] (x @ W), or ``transposed`` [N][K] (x @ W^T), optionally only its first n_rows rows -> the arm's packing"""
+    size, pack_fn, dtype, tail = _DENSE_PACK[arm]
+    lib = _lib.load()
+    w = _f32(w).contiguous()
+    n, k = w.shape if transposed else w.shape[::-1]
+    n = n if n_rows is None else n_rows
+    out = torch.empty(int(getattr(lib, size)(k, n)), dtype=dtype, device=w.device)
+    check(getattr(lib, pack_fn)(_p(w), _p(out), k, n, *((1, k) if transposed else (n, 1)), *tail, _stream()), pack_fn)
+    return out
+
+
+def _pack_conv3(arm, w_oihw):
+    size, pack_fn, dtype = _CONV3_PACK[arm]
+    lib = _lib.load()
+    w = _f32(w_oihw).contiguous()
+    cout, cin = w.shape[:2]
+    out = torch.empty(int(getattr(lib, size)(cin, cout)), dtype=dtype, device=w.device)
+    check(getattr(lib, pack_fn)(_p(w), _p(out), cin, cout, _stream()), pack_fn)
+    return out
+
+
 # ------------------------------------------------------------------ implicit GEMM
 def pack_dense_kn_bf16(w):
     """Conv1D weight [nx][nf] -> bf16 fragment packing for vf_gemm_bf16"""
-    lib = _lib.load()
-    w = _f32(w).contiguous()
-    k, n = w.shape
-    out = torch.empty(int(lib.vf_gemm_bf16_packed_elems(k, n)), dtype=torch.bfloat16, device=w.device)
-    check(lib.vf_gemm_bf16_pack(_p(w), _p(out), k, n, n, 1, 1, 0, _stream()), 'vf_gemm_bf16_pack')
-    return out
+    return _pack_dense('bf16', w, False)
 
 
 def pack_bf16_multi(items):
@@ -120,92 +146,42 @@ def pack_bf16_multi(items):
 
 def pack_dense_nk_bf16(w, n_rows=None):
     """transposed weight [N][K] (x @ W^T; tied LM head, 1x1 conv [Cout][Cin]) -> bf16 packing"""
-    lib = _lib.load()
-    w = _f32(w).contiguous()
-    n, k = w.shape
-    n = n if n_rows is None else n_rows
-    out = torch.empty(int(lib.vf_gemm_bf16_packed_elems(k, n)), dtype=torch.bfloat16, device=w.device)
-    check(lib.vf_gemm_bf16_pack(_p(w), _p(out), k, n, 1, k, 1, 0, _stream()), 'vf_gemm_bf16_pack')
-    return out
+    return _pack_dense('bf16', w, True, n_rows)
 
 
 def pack_conv3_bf16(w_oihw):
-    lib = _lib.load()
-    w = _f32(w_oihw).contiguous()
-    cout, cin = w.shape[:2]
-    out = torch.empty(int(lib.vf_conv3_bf16_packed_elems(cin, cout)), dtype=torch.bfloat16, device=w.device)
-    check(lib.vf_conv3_bf16_pack(_p(w), _p(out), cin, cout, _stream()), 'vf_conv3_bf16_pack')
-    return out
+    return _pack_conv3('bf16', w_oihw)
 
 
 def pack_conv3_x6(w_oihw):
     """OIHW fp32 3x3 weight -> three fragment-packed bf16 planes (exact split w = h + m + l) for vf_conv3_halo_x6"""
-    lib = _lib.load()
-    w = _f32(w_oihw).contiguous()
-    cout, cin = w.shape[:2]
-    out = torch.empty(int(lib.vf_conv3_x6_packed_elems(cin, cout)), dtype=torch.bfloat16, device=w.device)
-    check(lib.vf_conv3_x6_pack(_p(w), _p(out), cin, cout, _stream()), 'vf_conv3_x6_pack')
-    return out
+    return _pack_conv3('x6', w_oihw)
 
 
 def pack_conv3_x3h(w_oihw):
     """OIHW fp32 3x3 weight -> two fragment-packed f16 planes of w * S (S a power of two, 1/S stored behind them) for
     vf_conv3_halo_x3h"""
-    lib = _lib.load()
-    w = _f32(w_oihw).contiguous()
-    cout, cin = w.shape[:2]
-    out = torch.empty(int(lib.vf_conv3_x3h_packed_elems(cin, cout)), dtype=torch.float16, device=w.device)
-    check(lib.vf_conv3_x3h_pack(_p(w), _p(out), cin, cout, _stream()), 'vf_conv3_x3h_pack')
-    return out
-
-
-def conv3_x3h_supported(mode, Cin, Cout, Hout, Wout):
-    """shape rules of vf_conv3_halo_x3h: the x6 kernel's, plus the 16x16 -> 8x8 stride-2 convolution (two images per tile)"""
-    if mode == MODE_CONV3_S2PAD and Hout == 8 and Wout == 8 and Cin % 32 == 0 and Cout % 128 == 0:
-        return True
-    return conv3_x6_supported(mode, Cin, Cout, Hout, Wout)
+    return _pack_conv3('x3h', w_oihw)
 
 
 def pack_dense_kn_x6(w):
     """Conv1D weight [nx][nf] -> 3-plane split packing for vf_gemm_x6"""
-    lib = _lib.load()
-    w = _f32(w).contiguous()
-    k, n = w.shape
-    out = torch.empty(int(lib.vf_gemm_x6_packed_elems(k, n)), dtype=torch.bfloat16, device=w.device)
-    check(lib.vf_gemm_x6_pack(_p(w), _p(out), k, n, n, 1, _stream()), 'vf_gemm_x6_pack')
-    return out
+    return _pack_dense('x6', w, False)
 
 
 def pack_dense_nk_x6(w, n_rows=None):
     """transposed weight [N][K] (x @ W^T; tied LM head, 1x1 conv [Cout][Cin]) -> 3-plane split packing"""
-    lib = _lib.load()
-    w = _f32(w).contiguous()
-    n, k = w.shape
-    n = n if n_rows is None else n_rows
-    out = torch.empty(int(lib.vf_gemm_x6_packed_elems(k, n)), dtype=torch.bfloat16, device=w.device)
-    check(lib.vf_gemm_x6_pack(_p(w), _p(out), k, n, 1, k, _stream()), 'vf_gemm_x6_pack')
-    return out
+    return _pack_dense('x6', w, True, n_rows)
 
 
 def pack_dense_kn_x3h(w):
     """Conv1D weight [nx][nf] -> two-plane split-fp16 packing (w * S, 1/S behind the planes) for vf_gemm_x3h"""
-    lib = _lib.load()
-    w = _f32(w).contiguous()
-    k, n = w.shape
-    out = torch.empty(int(lib.vf_gemm_x3h_packed_elems(k, n)), dtype=torch.float16, device=w.device)
-    check(lib.vf_gemm_x3h_pack(_p(w), _p(out), k, n, n, 1, _stream()), 'vf_gemm_x3h_pack')
-    return out
+    return _pack_dense('x3h', w, False)
 
 
 def pack_dense_nk_x3h(w, n_rows=None):
     """transposed weight [N][K] (x @ W^T; tied LM head, 1x1 conv [Cout][Cin]) -> two-plane split-fp16 packing"""
-    lib = _lib.load()
-    w = _f32(w).contiguous()
-    n, k = w.shape
-    n = n if n_rows is None else n_rows
-    out = torch.empty(int(lib.vf_gemm_x3h_packed_elems(k, n)), dtype=torch.float16, device=w.device)
-    check(lib.vf_gemm_x3h_pack(_p(w), _p(out), k, n, 1, k, _stream()), 'vf_gemm_x3h_pack')
-    return out
+    return _pack_dense('x3h', w, True, n_rows)
 
 
 def gemm_x6_splitk(x, w_packed, M, Cin, Cout, dst, splits, lda=None, accumulate=True):
@@ -224,6 +200,38 @@ def conv3_x6_supported(mode, Cin, Cout, Hout, Wout):
     if mode not in (MODE_CONV3_S1, MODE_CONV3_UP2, MODE_CONV3_S2PAD) or Cin % 32 or Cout % 128:
         return False
     return (Hout % 8 == 0 and Wout % 16 == 0) or (mode == MODE_CONV3_S1 and Hout == 8 and Wout == 8)
+
+
+def conv3_x3h_supported(mode, Cin, Cout, Hout, Wout):
+    """shape rules of vf_conv3_halo_x3h: the x6 kernel's, plus the 16x16 -> 8x8 stride-2 convolution (two images per tile)"""
+    if mode == MODE_CONV3_S2PAD and Hout == 8 and Wout == 8 and Cin % 32 == 0 and Cout % 128 == 0:
+        return True
+    return conv3_x6_supported(mode, Cin, Cout, Hout, Wout)
+
+
+# the codec's call sites (vqgan.py, vqgan_train.py, lpips.py) name a launch's arithmetic ("arm"); igemm takes it as boolean keywords
+ARM_KW = {'f32': {}, 'x6': dict(x6=True), 'x3h': dict(x3h=True), 'bf16': dict(bf16=True)}
+
+
+def conv3_arm(mode, Cin, Cout, Hout, Wout, activations=False, res=False):
+    """the arm of a 3x3 convolution whose weight is packed for the launch (codebook trainer, LPIPS): 'small' = the small-cout kernel
+    (conv3_small_cout, no residual), else 'x6' where conv3_x6_supported — 'x3h' on top for forward ``activations`` (O(1) magnitudes;
+    gradients, ~1e-6, stay on x6, which has no range condition: DESIGN.md 4) — else the native 'f32'"""
+    if not res and conv3_small_cout_supported(mode, Cin, Cout, Hout, Wout):
+        return 'small'
+    if conv3_x6_supported(mode, Cin, Cout, Hout, Wout):
+        return 'x3h' if activations else 'x6'
+    return 'f32'
+
+
+def pack_conv3(arm, w_oihw):
+    """3x3 OIHW weight -> the packing igemm(**ARM_KW[arm]) reads"""
+    return {'f32': pack_conv_oihw, 'x6': pack_conv3_x6, 'x3h': pack_conv3_x3h, 'bf16': pack_conv3_bf16}[arm](w_oihw)
+
+
+def pack_dense_nk_arm(arm, w, n_rows=None):
+    """transposed weight [N][K] -> the packing igemm(**ARM_KW[arm]) reads"""
+    return {'f32': pack_dense_nk, 'x6': pack_dense_nk_x6, 'x3h': pack_dense_nk_x3h, 'bf16': pack_dense_nk_bf16}[arm](w, n_rows)
 
 
 def gemm_bf16_splitk(x, w_packed, M, Cin, Cout, dst, splits, lda=None, accumulate=True):

@@ -28,8 +28,58 @@ from .weights import vqgan_layout
 _IGNORED = re.compile(r'(perceptual_loss\..*)|(loss\..*)')     # vqgan_th.py:322
 
 
+_GN_STAT_WIDTHS = (128, 256, 512, 1024)       # output widths at which the halo kernels (and the x3h conv_in) emit GroupNorm partial statistics
+
+
 class _Conv:
-    __slots__ = ('wp', 'wp16', 'wp6', 'wp3h', 'bias', 'cin', 'cout', 'k', 'w_raw')
+    """one convolution (or the fused q|k|v projection of an AttnBlock): ``packed`` = {arm: packed weight} for the arms _layer_arms keeps"""
+    __slots__ = ('packed', 'bias', 'cin', 'cout', 'k', 'w_raw')
+
+
+def _layer_arms(k, cin, cout, name, conv_arith, decoder_precision, dense_x3h):
+    """the arms a layer keeps a packing for, in packing order — the static half of the choice of arithmetic, _arm is the
+    other.  'f32' = native f32 MFMA, 'x6' / 'x3h' = the fp32-equivalent splits, 'bf16' = the decoder's tolerance arm, 'conv_in_x3h' = the
+    matrix-pipe form of the 3-channel conv_in."""
+    tile3 = k == 3 and cin % 32 == 0 and cout % 128 == 0               # what the halo kernels (x6, x3h, bf16) tile
+    tile1 = k == 1 and cin % 64 == 0 and cout >= 64                    # ... and the split GEMMs
+    split = conv_arith in ('x6', 'x3h') and (tile3 or tile1)
+    x3h = split and conv_arith == 'x3h' and (k == 3 or dense_x3h)      # VF_VQ_DENSE_X3H=0: the 1x1 layers stay on the 6-product GEMM
+    if name.endswith('.qkv'):                                          # one [C][3C] GEMM, fp32 in and out: its best exact arm only
+        return ['x3h'] if x3h else ['x6'] if split else ['f32']
+    arms = []
+    if cin % 32 == 0:
+        arms.append('f32')
+    if conv_arith == 'x3h' and k == 3 and cin == 3 and cout % 128 == 0:
+        arms.append('conv_in_x3h')
+    if split:
+        arms.append('x6')
+    if x3h:
+        arms.append('x3h')
+    if decoder_precision == 'bf16' and (name.startswith('decoder.') or name == 'post_quant_conv') and (tile3 or k == 1 and cin % 64 == 0):
+        arms.append('bf16')
+    return arms
+
+
+def _arm(c, mode, Ho=0, Wo=0, pro=False, res=False):
+    """the arm one launch of layer ``c`` takes — the only place that decides it: 'small' (a 3x3 convolution the small-cout kernel
+    takes: conv_out) or the first of 'bf16' > 'x3h' > 'x6' > 'f32' that the layer keeps a packing for and whose kernel takes the launch
+    (``mode``, output ``Ho`` x ``Wo``, GroupNorm prologue ``pro``, residual ``res``)."""
+    if mode == ops.MODE_GEMM:                                          # 1x1 / q|k|v
+        if 'bf16' in c.packed and not pro:                             # the bf16 GEMM has no prologue
+            return 'bf16'
+        return 'x3h' if 'x3h' in c.packed else 'x6' if 'x6' in c.packed else 'f32'
+    if not res and ops.conv3_small_cout_supported(mode, c.cin, c.cout, Ho, Wo):
+        return 'small'
+    # bf16 on the halo-kernel shapes only.  So the 8x8 stage (512 channels, first 11 convs of the decoder) stays fp32 even in the bf16 arm:
+    # rounding there is amplified by every later layer (8.3e-2 max pixel error with it in bf16 vs 4.6e-2 without) and it is ~1 ms of work
+    if 'bf16' in c.packed and mode in (ops.MODE_CONV3_S1, ops.MODE_CONV3_UP2) and Ho % 8 == 0 and Wo % 16 == 0:
+        return 'bf16'
+    if not (mode == ops.MODE_CONV3_S2PAD and pro):                     # the split stride-2 kernels have no prologue
+        if 'x3h' in c.packed and ops.conv3_x3h_supported(mode, c.cin, c.cout, Ho, Wo):
+            return 'x3h'
+        if 'x6' in c.packed and ops.conv3_x6_supported(mode, c.cin, c.cout, Ho, Wo):
+            return 'x6'
+    return 'f32'
 
 
 class VQGAN:
@@ -58,7 +108,6 @@ class VQGAN:
         self._sd = None          # reference-keyed fp32 tensors on the device
         self._conv = {}
         self._norm = {}
-        self._qkv = {}
         self.training = False
         # conv_arith='x3h': 1x1 convolutions / q|k|v projections on the 3-product split-fp16 GEMM (VF_VQ_DENSE_X3H=0: 6-product x6); read
         # per instance, like every other environment knob of the package
@@ -126,39 +175,30 @@ class VQGAN:
     def _upload(self):
         dev = self.device
         h = self._sd_host
-        self._conv, self._norm, self._qkv = {}, {}, {}
+        self._conv, self._norm = {}, {}
         self._act16_cache = {}
 
         def dev_t(name):
             return torch.from_numpy(h[name]).to(dev, torch.float32).contiguous()
 
-        def conv(name):
-            w = dev_t(name + '.weight')
+        def record(name, w, bias):
+            """w: OIHW, or [N][K] for the fused projection"""
             c = _Conv()
-            c.cout, c.cin, c.k = w.shape[0], w.shape[1], w.shape[2]
-            c.bias = dev_t(name + '.bias')
-            c.w_raw = w
-            c.wp = ops.pack_conv_oihw(w) if c.cin % 32 == 0 else None
-            c.wp16 = None
-            c.wp6 = None
-            c.wp3h = None
-            split = self.conv_arith in ('x6', 'x3h')
-            if self.conv_arith == 'x3h' and c.k == 3 and c.cin == 3 and c.cout % 128 == 0:
-                c.wp3h = ops.pack_conv_in_x3h(w)
-            if split and c.k == 3 and c.cin % 32 == 0 and c.cout % 128 == 0:
-                c.wp6 = ops.pack_conv3_x6(w)
-                if self.conv_arith == 'x3h':
-                    c.wp3h = ops.pack_conv3_x3h(w)
-            elif split and c.k == 1 and c.cin % 64 == 0 and c.cout >= 64:
-                c.wp6 = ops.pack_dense_nk_x6(w.reshape(c.cout, c.cin))
-                if self.conv_arith == 'x3h' and self.dense_x3h:       # 1x1 convolutions on the 3-product GEMM too (csrc/gemm_x3h.hip)
-                    c.wp3h = ops.pack_dense_nk_x3h(w.reshape(c.cout, c.cin))
-            if self.decoder_precision == 'bf16' and (name.startswith('decoder.') or name == 'post_quant_conv'):
-                if c.k == 3 and c.cin % 32 == 0 and c.cout % 128 == 0:
-                    c.wp16 = ops.pack_conv3_bf16(w)
-                elif c.k == 1 and c.cin % 64 == 0:
-                    c.wp16 = ops.pack_dense_nk_bf16(w.reshape(c.cout, c.cin))
+            c.cout, c.cin, c.k = w.shape[0], w.shape[1], w.shape[2] if w.dim() == 4 else 1
+            c.bias, c.w_raw, c.packed = bias, w, {}
+            for arm in _layer_arms(c.k, c.cin, c.cout, name, self.conv_arith, self.decoder_precision, self.dense_x3h):
+                if arm == 'conv_in_x3h':
+                    c.packed[arm] = ops.pack_conv_in_x3h(w)
+                elif arm == 'f32' and w.dim() == 4:
+                    c.packed[arm] = ops.pack_conv_oihw(w)
+                elif c.k == 3:
+                    c.packed[arm] = ops.pack_conv3(arm, w)
+                else:
+                    c.packed[arm] = ops.pack_dense_nk_arm(arm, w.reshape(c.cout, c.cin))
             self._conv[name] = c
+
+        def conv(name):
+            record(name, dev_t(name + '.weight'), dev_t(name + '.bias'))
 
         def norm(name):
             self._norm[name] = (dev_t(name + '.weight'), dev_t(name + '.bias'))
@@ -175,11 +215,7 @@ class VQGAN:
                 c = args[0]
                 # fused q|k|v projection: one [C][3C] GEMM
                 w = torch.cat([dev_t(f'{name}.{p}.weight').reshape(c, c) for p in ('q', 'k', 'v')], 0)   # [3C][C] (out,in)
-                b = torch.cat([dev_t(f'{name}.{p}.bias') for p in ('q', 'k', 'v')], 0)
-                if self.conv_arith == 'x3h' and self.dense_x3h and c % 64 == 0:
-                    self._qkv[name] = (ops.pack_dense_nk_x3h(w), b)
-                else:
-                    self._qkv[name] = (ops.pack_dense_nk_x6(w) if self.conv_arith in ('x6', 'x3h') and c % 64 == 0 else ops.pack_dense_nk(w), b)
+                record(name + '.qkv', w, torch.cat([dev_t(f'{name}.{p}.bias') for p in ('q', 'k', 'v')], 0))
                 conv(name + '.proj_out')
             elif kind == 'norm_swish':
                 norm(name)
@@ -194,66 +230,52 @@ class VQGAN:
         torch.cuda.synchronize(dev)
 
     # ------------------------------------------------------------------ building blocks (NHWC rows)
+    def _gn_part(self, cout, n, Ho, Wo, device):
+        """the halo kernels also emit the GroupNorm partial statistics of what they store, so the consumer's norm (_gn) only runs the tiny
+        finalize instead of re-reading the activation: the buffer for them, or None"""
+        return ops.new_gn_part(n, Ho, Wo, device) if self.fuse_gn_stats and cout in _GN_STAT_WIDTHS else None
+
     def _conv3(self, x, name, n, H, W, mode=ops.MODE_CONV3_S1, pro=None, pro_swish=True, res=None, o16=False):
-        """``o16``: write the output as bf16 (bf16 arm, halo-kernel shapes only); a bf16 ``x`` is read as such.  The activation stream
-        switches to bf16 once (at the 16 -> 32 upsample convolution, see _run_plan) and stays bf16 to conv_out."""
+        """-> (rows, Ho, Wo, GroupNorm partials of the rows or None).  ``o16``: write the output as bf16 (bf16 arm, halo-kernel shapes only);
+        a bf16 ``x`` is read as such.  The activation stream switches to bf16 once (at the 16 -> 32 upsample convolution, see _run_plan) and
+        stays bf16 to conv_out."""
         c = self._conv[name]
         a16 = x.dtype == torch.bfloat16
-        if mode == ops.MODE_CONV3_S2PAD:
-            Ho, Wo = H // 2, W // 2
-        elif mode == ops.MODE_CONV3_UP2:
-            Ho, Wo = H * 2, W * 2
-        else:
-            Ho, Wo = H, W
-        if res is None and ops.conv3_small_cout_supported(mode, c.cin, c.cout, Ho, Wo):      # conv_out (-> 3 channels)
-            self._stats_of = None
-            return ops.conv3_small_cout(x, c.w_raw, c.bias, n, H, W, c.cin, c.cout, pro=pro, pro_swish=pro_swish), Ho, Wo
+        Ho, Wo = (H // 2, W // 2) if mode == ops.MODE_CONV3_S2PAD else (H * 2, W * 2) if mode == ops.MODE_CONV3_UP2 else (H, W)
+        arm = _arm(c, mode, Ho, Wo, pro=pro is not None, res=res is not None)
+        if arm == 'small':                                                                   # conv_out (-> 3 channels)
+            return ops.conv3_small_cout(x, c.w_raw, c.bias, n, H, W, c.cin, c.cout, pro=pro, pro_swish=pro_swish), Ho, Wo, None
         o16 = o16 or a16
-        out = torch.empty((n * Ho * Wo, c.cout), dtype=torch.bfloat16 if o16 else torch.float32, device=x.device)
-        # the 8x8 stage (512 channels, first 11 convs of the decoder) stays fp32 even in the bf16 arm: rounding there is
-        # amplified by every later layer (8.3e-2 max pixel error with it in bf16 vs 4.6e-2 without) and it is ~1 ms of work
-        bf16 = (c.wp16 is not None and mode in (ops.MODE_CONV3_S1, ops.MODE_CONV3_UP2) and Ho % 8 == 0 and Wo % 16 == 0)
-        if o16 and not bf16:
+        if o16 and arm != 'bf16':
             raise ops._lib.VfError(f'{name}: bf16 activations need the bf16 convolution arm (halo-kernel shape)')
-        x3h = (not bf16 and c.wp3h is not None and ops.conv3_x3h_supported(mode, c.cin, c.cout, Ho, Wo)
-               and not (mode == ops.MODE_CONV3_S2PAD and pro is not None))
-        x6 = (not bf16 and not x3h and c.wp6 is not None and ops.conv3_x6_supported(mode, c.cin, c.cout, Ho, Wo)
-              and not (mode == ops.MODE_CONV3_S2PAD and pro is not None))
-        # the halo kernels also emit the GroupNorm partial statistics of what they store, so the consumer's norm
-        # (_gn) only runs the tiny finalize instead of re-reading the activation
-        part = None
-        if (bf16 or x6 or x3h) and self.fuse_gn_stats and c.cout in (128, 256, 512, 1024):
-            part = ops.new_gn_part(n, Ho, Wo, x.device)
-        ops.igemm(x, c.wp16 if bf16 else c.wp3h if x3h else c.wp6 if x6 else c.wp, n * Ho * Wo, c.cin, c.cout, out, bias=c.bias, res=res,
-                  mode=mode, pro=pro, pro_swish=pro_swish, Hin=H, Win=W, Hout=Ho, Wout=Wo, bf16=bf16, x6=x6, x3h=x3h, gn_part=part,
-                  a16=a16, o16=o16)
-        self._stats_of = (out, part) if part is not None else None
-        return out, Ho, Wo
+        out = torch.empty((n * Ho * Wo, c.cout), dtype=torch.bfloat16 if o16 else torch.float32, device=x.device)
+        part = self._gn_part(c.cout, n, Ho, Wo, x.device) if arm != 'f32' else None
+        ops.igemm(x, c.packed[arm], n * Ho * Wo, c.cin, c.cout, out, bias=c.bias, res=res, mode=mode, pro=pro, pro_swish=pro_swish, Hin=H, Win=W,
+                  Hout=Ho, Wout=Wo, gn_part=part, a16=a16, o16=o16, **ops.ARM_KW[arm])
+        return out, Ho, Wo, part
 
     def _conv1(self, x, name, M, pro=None, pro_swish=False, rows_per_img=0, res=None):
         c = self._conv[name]
         a16 = x.dtype == torch.bfloat16           # a bf16 activation stream (nin_shortcut of the 64x64 level): bf16 in, bf16 out
-        out = torch.empty((M, c.cout), dtype=x.dtype, device=x.device)
-        bf16 = c.wp16 is not None and pro is None
-        if a16 and not (bf16 and res is None):
+        arm = _arm(c, ops.MODE_GEMM, pro=pro is not None)
+        if a16 and not (arm == 'bf16' and res is None):
             raise ops._lib.VfError(f'{name}: bf16 activations need the plain bf16 GEMM')
-        x3h = not bf16 and c.k == 1 and c.wp3h is not None
-        x6 = not bf16 and not x3h and c.wp6 is not None
-        ops.igemm(x, c.wp16 if bf16 else c.wp3h if x3h else c.wp6 if x6 else c.wp, M, c.cin, c.cout, out, bias=c.bias, res=res, pro=pro,
-                  pro_swish=pro_swish, pro_rows_per_img=rows_per_img, bf16=bf16, x6=x6, x3h=x3h, a16=a16, o16=a16)
+        out = torch.empty((M, c.cout), dtype=x.dtype, device=x.device)
+        ops.igemm(x, c.packed[arm], M, c.cin, c.cout, out, bias=c.bias, res=res, pro=pro, pro_swish=pro_swish, pro_rows_per_img=rows_per_img,
+                  a16=a16, o16=a16, **ops.ARM_KW[arm])
         return out
 
-    def _gn(self, x, name, n, HW, C):
+    def _gn(self, x, name, n, HW, C, part=None):
+        """GroupNorm as the prologue of the consuming convolution; ``part`` = the partial statistics the kernel that produced ``x`` wrote"""
         gamma, beta = self._norm[name]
-        if self._stats_of is not None and self._stats_of[0] is x:
-            mean_c, scale_c = ops.groupnorm_finalize(self._stats_of[1], gamma, n, HW, C, 32, 1e-6)
+        if part is not None:
+            mean_c, scale_c = ops.groupnorm_finalize(part, gamma, n, HW, C, 32, 1e-6)
         else:
             if x.dtype != torch.float32:
                 raise ops._lib.VfError(f'{name}: a bf16 activation carries its GroupNorm statistics from the producing kernel (fuse_gn_stats)')
             mean_c, scale_c = ops.groupnorm_stats(x, gamma, n, HW, C, 32, 1e-6)
         return (mean_c, scale_c, beta)
 
-    _stats_of = None          # (tensor, partials) of the most recent halo-conv output
     # bf16 arm only: R > 0 = bf16 activations between the decoder's layers from resolution R x R up (see _run_plan).  Default 128: the last
     # level holds 6 of the decoder's 9.5 ms and costs one uint8 level of the stated bound (max 7 -> 8, mean |err| 4.4e-3 -> 4.6e-3;
     # R = 32: max 10, 5.3e-3 — tests/test_hip_bf16.py); 0 = fp32 activations throughout (the round-3 form)
@@ -261,27 +283,24 @@ class VQGAN:
     fuse_gn_stats = True
     fused_attention = True    # AttnBlock core in one kernel where the shape allows (False: batched GEMMs + row softmax, kept for A/B)
 
-    def _res(self, x, name, n, H, W, cin, cout):
-        """ResnetBlock.forward, vqgan_th.py:78-90"""
-        p1 = self._gn(x, name + '.norm1', n, H * W, cin)
-        h, _, _ = self._conv3(x, name + '.conv1', n, H, W, pro=p1)
-        p2 = self._gn(h, name + '.norm2', n, H * W, cout)
+    def _res(self, x, part, name, n, H, W, cin, cout):
+        """ResnetBlock.forward, vqgan_th.py:78-90 -> (rows, their GroupNorm partials or None)"""
+        p1 = self._gn(x, name + '.norm1', n, H * W, cin, part)
+        h, _, _, hpart = self._conv3(x, name + '.conv1', n, H, W, pro=p1)
+        p2 = self._gn(h, name + '.norm2', n, H * W, cout, hpart)
         sc = x if cin == cout else self._conv1(x, name + '.nin_shortcut', n * H * W)
-        out, _, _ = self._conv3(h, name + '.conv2', n, H, W, pro=p2, res=sc)
-        return out
+        out, _, _, part = self._conv3(h, name + '.conv2', n, H, W, pro=p2, res=sc)
+        return out, part
 
-    def _attn(self, x, name, n, H, W, C):
+    def _attn(self, x, part, name, n, H, W, C):
         """AttnBlock.forward, vqgan_th.py:120-144"""
         HW = H * W
         M = n * HW
-        pro = self._gn(x, name + '.norm', n, HW, C)
-        wp, b = self._qkv[name]
-        qkv = torch.empty((M, 3 * C), dtype=torch.float32, device=x.device)
-        ops.igemm(x, wp, M, C, 3 * C, qkv, bias=b, pro=pro, pro_swish=False, pro_rows_per_img=HW, x6=wp.dtype == torch.bfloat16,
-                  x3h=wp.dtype == torch.float16)
+        pro = self._gn(x, name + '.norm', n, HW, C, part)
+        qkv = self._conv1(x, name + '.qkv', M, pro=pro, rows_per_img=HW)
         if self.fused_attention and ops.attn_spatial_supported(HW, C):
-            # scores, softmax and p.v in one kernel: the [HW][HW] matrix never leaves the CU (csrc/attn_spatial.hip)
-            a = ops.attn_spatial(qkv, n, HW, C, float(int(C) ** (-0.5)), x3h=self.conv_arith == 'x3h' and self.dense_x3h)
+            # scores, softmax and p.v in one kernel (csrc/attn_spatial.hip: the [HW][HW] matrix never leaves the CU), on the projection's arm
+            a = ops.attn_spatial(qkv, n, HW, C, float(int(C) ** (-0.5)), x3h=_arm(self._conv[name + '.qkv'], ops.MODE_GEMM, pro=True) == 'x3h')
             return self._conv1(a, name + '.proj_out', M, res=x)
         q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
         # scores[b] = q_b @ k_b^T : B[kk=c][nn=key] = k[key][c]
@@ -299,7 +318,7 @@ class VQGAN:
 
     def _act16_plan_ok(self, plan, idx, H, W):
         """can the activation stream switch to bf16 at the 'up' convolution ``plan[idx]`` (output H x W)?  Only if EVERY layer from there to
-        conv_out can take it: each 3x3 convolution on the bf16 halo arm (``wp16``: cin % 32 == 0, cout % 128 == 0, tile-aligned output) or
+        conv_out can take it: each 3x3 convolution on the bf16 halo arm (_arm: a bf16 packing and a tile-aligned output) or
         the small-cout kernel (conv_out), each GroupNorm fed by fused partial statistics (producer cout in 128 / 256 / 512 / 1024), each
         nin_shortcut on the plain bf16 GEMM, no AttnBlock in the bf16 stretch.  Otherwise (e.g. ch = 64 or 96: a 64- or 384-channel top
         level) the decoder keeps fp32 activations and the per-layer choice of arithmetic, as before decoder_act16 existed."""
@@ -308,12 +327,12 @@ class VQGAN:
         if hit is not None:
             return hit
 
-        def conv_ok(name, mode, h, w, feeds_norm=True):
+        def conv_ok(name, mode, h, w, res=False, feeds_norm=True):
             c = self._conv[name]
-            ho, wo = (h * 2, w * 2) if mode == ops.MODE_CONV3_UP2 else (h, w)
-            if ops.conv3_small_cout_supported(mode, c.cin, c.cout, ho, wo):
-                return True                                              # conv_out: reads bf16, writes the fp32 image
-            return (c.wp16 is not None and ho % 8 == 0 and wo % 16 == 0 and (not feeds_norm or c.cout in (128, 256, 512, 1024)))
+            up = mode == ops.MODE_CONV3_UP2                              # (the only convolution of the stretch without a GroupNorm prologue)
+            arm = _arm(c, mode, h << up, w << up, pro=not up, res=res)
+            # conv_out ('small') reads bf16 and writes the fp32 image
+            return arm == 'small' or (arm == 'bf16' and (not feeds_norm or c.cout in _GN_STAT_WIDTHS))
 
         ok = self.fuse_gn_stats and conv_ok(plan[idx][1], ops.MODE_CONV3_UP2, H // 2, W // 2)
         h, w = H, W
@@ -321,10 +340,9 @@ class VQGAN:
             if not ok:
                 break
             if kind == 'res':
-                ok = conv_ok(name + '.conv1', ops.MODE_CONV3_S1, h, w) and conv_ok(name + '.conv2', ops.MODE_CONV3_S1, h, w)
+                ok = conv_ok(name + '.conv1', ops.MODE_CONV3_S1, h, w) and conv_ok(name + '.conv2', ops.MODE_CONV3_S1, h, w, res=True)
                 if ok and args[0] != args[1]:
-                    sc = self._conv[name + '.nin_shortcut']
-                    ok = sc.wp16 is not None and sc.k == 1
+                    ok = _arm(self._conv[name + '.nin_shortcut'], ops.MODE_GEMM) == 'bf16'
             elif kind == 'up':
                 ok = conv_ok(name, ops.MODE_CONV3_UP2, h, w)
                 h, w = h * 2, w * 2
@@ -337,39 +355,35 @@ class VQGAN:
         self._act16_cache[key] = bool(ok)
         return bool(ok)
 
-    def _run_plan(self, plan, x, n, H, W, first_is_image=False):
+    def _run_plan(self, plan, x, n, H, W):
+        part = pro = None         # travel with x: the GroupNorm partials its producing kernel wrote; a norm waiting for the next conv
         for idx, (kind, name, args) in enumerate(plan):
             if kind == 'conv3':
                 c = self._conv[name]
-                if c.wp is None:      # 3-channel conv_in (fused uint8 -> [-1,1])
-                    if c.wp3h is not None and ops.conv_in_x3h_supported(H, W, c.cout):      # matrix-pipe form + fused GN statistics
-                        part = ops.new_gn_part(n, H, W, x.device) if self.fuse_gn_stats and c.cout in (128, 256, 512, 1024) else None
-                        x = ops.conv_in(x, c.w_raw, c.bias, n, H, W, c.cout, wp3h=c.wp3h, gn_part=part).view(n * H * W, c.cout)
-                        self._stats_of = (x, part) if part is not None else None
-                    else:
-                        x = ops.conv_in(x, c.w_raw, c.bias, n, H, W, c.cout).view(n * H * W, c.cout)
-                        self._stats_of = None
+                if 'f32' not in c.packed:      # 3-channel conv_in (fused uint8 -> [-1,1]); matrix-pipe form + fused GN statistics where packed
+                    mp = c.packed.get('conv_in_x3h') if ops.conv_in_x3h_supported(H, W, c.cout) else None
+                    part = self._gn_part(c.cout, n, H, W, x.device) if mp is not None else None
+                    x = ops.conv_in(x, c.w_raw, c.bias, n, H, W, c.cout, None, mp, part).view(n * H * W, c.cout)     # (no out; packing; partials)
                 else:
-                    x, H, W = self._conv3(x, name, n, H, W, pro=self._pending_pro, pro_swish=True)
-                self._pending_pro = None
+                    x, H, W, part = self._conv3(x, name, n, H, W, pro=pro, pro_swish=True)
+                pro = None
             elif kind == 'res':
-                x = self._res(x, name, n, H, W, args[0], args[1])
+                x, part = self._res(x, part, name, n, H, W, args[0], args[1])
             elif kind == 'attn':
-                x = self._attn(x, name, n, H, W, args[0])
+                x, part = self._attn(x, part, name, n, H, W, args[0]), None
             elif kind == 'down':
-                x, H, W = self._conv3(x, name, n, H, W, mode=ops.MODE_CONV3_S2PAD)
+                x, H, W, part = self._conv3(x, name, n, H, W, mode=ops.MODE_CONV3_S2PAD)
             elif kind == 'up':
                 # decoder_act16 = R > 0: from the first upsample whose output is R x R or larger (R >= 32) the activations stay bf16 in HBM
                 # to conv_out; the stages below keep fp32 activations
                 o16 = bool(self.decoder_act16 and self.decoder_precision == 'bf16' and self.fuse_gn_stats and name.startswith('decoder.')
                            and H * 2 >= max(32, int(self.decoder_act16)) and (H * 2) % 8 == 0 and (W * 2) % 16 == 0
                            and x.dtype != torch.bfloat16 and self._act16_plan_ok(plan, idx, H * 2, W * 2))
-                x, H, W = self._conv3(x, name, n, H, W, mode=ops.MODE_CONV3_UP2, o16=o16)
+                x, H, W, part = self._conv3(x, name, n, H, W, mode=ops.MODE_CONV3_UP2, o16=o16)
             elif kind == 'norm_swish':
-                self._pending_pro = self._gn(x, name, n, H * W, args[0])   # folded into the next conv
+                pro = self._gn(x, name, n, H * W, args[0], part)           # folded into the next conv
         return x, H, W
 
-    _pending_pro = None
     _act16_cache = None
 
     # ------------------------------------------------------------------ encoder / decoder on NHWC

@@ -132,19 +132,16 @@ class VQGANTrainer:
             M = n * H * W
             out = torch.empty((M, cout), dtype=torch.float32, device=x.device)
             w2 = w.reshape(cout, cin)
-            if cin % 64 == 0 and cout >= 64:
-                ops.igemm(x, ops.pack_dense_nk_x6(w2), M, cin, cout, out, bias=bias, res=res, x6=True)
-            else:
-                ops.igemm(x, ops.pack_dense_nk(w2), M, cin, cout, out, bias=bias, res=res)
+            arm = 'x6' if cin % 64 == 0 and cout >= 64 else 'f32'
+            ops.igemm(x, ops.pack_dense_nk_arm(arm, w2), M, cin, cout, out, bias=bias, res=res, **ops.ARM_KW[arm])
             return out, H, W
         Ho, Wo = (H // 2, W // 2) if mode == ops.MODE_CONV3_S2PAD else (H * 2, W * 2) if mode == ops.MODE_CONV3_UP2 else (H, W)
-        if res is None and ops.conv3_small_cout_supported(mode, cin, cout, Ho, Wo):
+        arm = ops.conv3_arm(mode, cin, cout, Ho, Wo, activations=activations, res=res is not None)
+        if arm == 'small':
             return ops.conv3_small_cout(x, w, bias, n, H, W, cin, cout), Ho, Wo
         out = torch.empty((n * Ho * Wo, cout), dtype=torch.float32, device=x.device)
-        x6 = ops.conv3_x6_supported(mode, cin, cout, Ho, Wo)
-        x3h = x6 and activations
-        ops.igemm(x, ops.pack_conv3_x3h(w) if x3h else ops.pack_conv3_x6(w) if x6 else ops.pack_conv_oihw(w), n * Ho * Wo, cin, cout, out,
-                  bias=bias, res=res, mode=mode, Hin=H, Win=W, Hout=Ho, Wout=Wo, x6=x6 and not x3h, x3h=x3h)
+        ops.igemm(x, ops.pack_conv3(arm, w), n * Ho * Wo, cin, cout, out, bias=bias, res=res, mode=mode, Hin=H, Win=W, Hout=Ho, Wout=Wo,
+                  **ops.ARM_KW[arm])
         return out, Ho, Wo
 
     def _conv_fw(self, name, x, n, H, W, mode=ops.MODE_CONV3_S1, res=None):
