@@ -540,6 +540,38 @@ int vf_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n_img, int H, in
 size_t vf_camera_knn_workspace_bytes(int64_t N, int Q, int k);
 int vf_camera_knn_f32(const float* db, int64_t N, const float* queries, int Q, int k, float pos_weight, int32_t* idx, float* dist,
                       void* workspace, void* stream);
+/* distance table of a codebook (csrc/code_knn.hip; host: ops.codebook_distances, VQGAN.code_distances): replaces embedding both codes
+ * (embed_code, viewformer/models/utils_th.py:70-72) and subtracting, for every pair of codes at once.  E is the codebook as VQGAN keeps
+ * it, feature-major [D][ldE] fp32 (code c's embedding is E[0..D-1][c]); table [K][K] fp32,
+ *     T[a][b] = sum_{j=0..D-1} fl(fl(e_a[j] - e_b[j])^2),     summed left to right from 0, every operation rounded explicitly, no contraction:
+ * exactly symmetric and exactly 0 on the diagonal for finite embeddings; entries are >= 0 or NaN; a pure function of E.  Footprint: reads
+ * the K logical floats of each of E's D rows, writes exactly the K * K floats of table.  NULL or not 4-byte aligned E / table, or ldE < K:
+ * VF_ERR_BAD_ARG; K outside [1, 4096] or D < 1: VF_ERR_UNSUPPORTED; both before any launch. */
+int vf_codebook_dist_table_f32(const float* E, int D, int K, int64_t ldE, float* table, void* stream);
+/* image retrieval on VQ codes (csrc/code_knn.hip; host: ops.code_knn, scene_bank.SceneBank.similar): stands in for the outside
+ * image-retrieval system whose match file the reference reads (viewformer/evaluate/evaluate_sevenscenes.py:71-77,238-240).  db [N][ld_db]
+ * and queries [Q][ld_q] are int32; the first t * t entries of a row are a photo's codes, row-major over the t x t token grid.  For each
+ * query the k database rows with the smallest
+ *     d_w(q, m) = sum_p  min_{p' in W_w(p)}  table[q[p]][m[p']]        (W_w(p): the grid positions within Chebyshev distance `window` of p,
+ *                                                                        clipped at the grid's border)
+ * in ascending order, ties to the lowest index; idx [Q][k] (int32), dist [Q][k] the distances (may be NULL).  window = 0 with
+ * vf_codebook_dist_table_f32's table is the squared L2 distance of the two quantised latent maps; window = t - 1 the full one-sided
+ * Chamfer distance.  exclude: NULL, or int32 [Q] on the device: the database row that query q must not return (-1: none).
+ * Arithmetic: fp32; the inner minimum starts at +inf and takes a candidate iff candidate < current (a NaN table entry never enters); the
+ * outer sum runs over p = 0 .. t*t - 1 ascending with explicitly rounded additions, starting from the first term.  A query code outside
+ * [0, K) makes its term +inf; a database code outside [0, K) is skipped as a candidate; the table is never read out of bounds, whatever
+ * the codes hold.  Table entries are expected to be >= 0 or NaN (what vf_codebook_dist_table_f32 produces): the selection orders
+ * distances by their bits.  Selection is vf_camera_knn_f32's: 64-bit keys (distance bits << 32) | index, NaN canonical and last, a pure
+ * function of (db, query, table, window, exclude, k), independent of Q, tiling and grid.
+ * Footprint: reads the t * t logical codes of each of the N database and Q query rows (not the row gaps, nothing beyond row N), table
+ * rows of valid query codes, Q ints of exclude; writes exactly Q * k elements of idx and of dist where given, and at most
+ * vf_code_knn_workspace_bytes bytes of `workspace` (per-tile candidates; the query returns 0 for invalid shapes, and for N <= 256 where
+ * a single launch writes the result; 8-byte aligned).  k < 1, N < k (N < k + 1 with exclude), Q < 0, t < 1, K < 1, window outside
+ * [0, t - 1], ld_db or ld_q < t * t, NULL db / queries / table / idx (workspace where needed) or a misaligned pointer: VF_ERR_BAD_ARG;
+ * k > 32, N > 2^31 - 1, t > 16, K > 4096 or Q > 524 280: VF_ERR_UNSUPPORTED; both before any launch.  Q == 0 is a no-op. */
+size_t vf_code_knn_workspace_bytes(int64_t N, int Q, int k);
+int vf_code_knn_f32(const int32_t* db, int64_t N, int64_t ld_db, const int32_t* queries, int Q, int64_t ld_q, int t, const float* table,
+                    int K, int window, const int32_t* exclude, int k, int32_t* idx, float* dist, void* workspace, void* stream);
 /* the tail of the localization head in one launch (csrc/pose_tail.hip; host: ops.pose_tail, MIGT.localize_from_context): the pose
  * classifier's c_proj, MLP(n_state, 7) viewformer/models/migt.py:291-292,354, QuaternionPoseRepresentation's output branch :159-164 and
  * its reduce :123-129,150-154.  x [views * L][K] fp32 with row stride ldx (the GELU output of c_fc), W [K][7] as stored (x @ W + b),

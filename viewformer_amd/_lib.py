@@ -144,6 +144,9 @@ EXPORTS = {
     'vf_image_metrics_u8': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
     'vf_camera_knn_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'vf_camera_knn_f32': (c_int, [P, c_int64, P, c_int, c_int, c_float, P, P, P, P]),
+    'vf_codebook_dist_table_f32': (c_int, [P, c_int, c_int, c_int64, P, P]),
+    'vf_code_knn_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
+    'vf_code_knn_f32': (c_int, [P, c_int64, c_int64, P, c_int, c_int64, c_int, P, c_int, c_int, P, c_int, P, P, P, P]),
     'vf_pose_tail_f32': (c_int, [P, c_int64, P, P, c_float, c_int64, c_int, c_int, P, P, P, P]),
     # ---- bf16 arm (transformer dense layers, decoder convolutions)
     'vf_gemm_bf16_packed_elems': (c_size_t, [c_int, c_int]),

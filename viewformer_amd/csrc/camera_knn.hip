@@ -19,20 +19,17 @@
 //      looped over the group's queries; each thread keeps the keys of its KNN_R rows in registers, and k rounds of a workgroup-wide
 //      minimum (butterfly over wave shuffles, the four waves' minima through LDS, one barrier per round: the slots alternate) emit the
 //      tile's k candidates into the workspace [Q][ntiles][k].  A tile with fewer than k rows pads with ~0 keys.
-//   2. camera_knn_merge_kernel: one workgroup per query, the same k rounds over its ntiles * k candidates.
+//   2. knn_merge_kernel (knn_select.h, shared with code_knn.hip as are the key and the workgroup-wide minimum): one workgroup per
+//      query, the same k rounds over its ntiles * k candidates.
 // With a single tile (N <= KNN_TILE) the first kernel writes idx / dist itself and there is no second launch.
 #include "vf_common.h"
+#include "knn_select.h"
 #include "../../include/vf_hip.h"
 
 namespace {
 
-constexpr int KNN_THREADS = 256;
-constexpr int KNN_WAVES = KNN_THREADS / VF_WAVE;
 constexpr int KNN_R = 4;                               // database rows per thread
 constexpr int KNN_TILE = KNN_THREADS * KNN_R;          // database rows per workgroup
-constexpr int KNN_QG = 8;                              // queries per workgroup of the tile kernel
-constexpr int KNN_MAX_K = 32;
-constexpr unsigned long long KNN_NONE = ~0ull;
 
 __device__ __forceinline__ float knn_sumsq3(float a, float b, float c) {
     return __fadd_rn(__fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)), __fmul_rn(c, c));
@@ -77,32 +74,6 @@ __device__ __forceinline__ float knn_distance(const float* p, const KnnQuery& q,
     return (vx != vx || vy != vy || vz != vz) ? __int_as_float(0x7FC00000) : d;
 }
 
-__device__ __forceinline__ unsigned long long knn_key(float d, unsigned index) {
-    const unsigned bits = d != d ? 0x7FC00000u : __float_as_uint(d);
-    return ((unsigned long long)bits << 32) | index;
-}
-
-__device__ __forceinline__ unsigned long long knn_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-
-// workgroup-wide minimum: butterfly inside each wave, the waves' minima through `slot` (KNN_WAVES words), ONE barrier.  The caller
-// alternates between two slots from round to round, so a wave that is already in the next round cannot overwrite what a slower wave
-// still reads.
-__device__ __forceinline__ unsigned long long knn_block_min(unsigned long long m, unsigned long long* slot) {
-#pragma unroll
-    for (int o = VF_WAVE / 2; o > 0; o >>= 1) m = knn_min(m, __shfl_xor(m, o, VF_WAVE));
-    if ((threadIdx.x & (VF_WAVE - 1)) == 0) slot[threadIdx.x / VF_WAVE] = m;
-    __syncthreads();
-    unsigned long long r = slot[0];
-#pragma unroll
-    for (int w = 1; w < KNN_WAVES; ++w) r = knn_min(r, slot[w]);
-    return r;
-}
-
-__device__ __forceinline__ void knn_emit(unsigned long long key, int32_t* __restrict__ idx, float* __restrict__ dist, long long at) {
-    idx[at] = (int32_t)(unsigned)key;
-    if (dist) dist[at] = __uint_as_float((unsigned)(key >> 32));
-}
-
 __global__ __launch_bounds__(KNN_THREADS) void camera_knn_tile_kernel(const float* __restrict__ db, long long N, const float* __restrict__ queries,
                                                                      int Q, int k, float pos_weight, int ntiles,
                                                                      unsigned long long* __restrict__ cand, int32_t* __restrict__ idx,
@@ -141,25 +112,6 @@ __global__ __launch_bounds__(KNN_THREADS) void camera_knn_tile_kernel(const floa
     }
 }
 
-__global__ __launch_bounds__(KNN_THREADS) void camera_knn_merge_kernel(const unsigned long long* __restrict__ cand, long long n, int k,
-                                                                      int32_t* __restrict__ idx, float* __restrict__ dist) {
-    __shared__ unsigned long long red[2][KNN_WAVES];
-    const int tid = threadIdx.x;
-    const long long q = blockIdx.x;
-    const unsigned long long* c = cand + q * n;
-    unsigned long long lower = 0;
-    for (int r = 0; r < k; ++r) {
-        unsigned long long m = KNN_NONE;
-        for (long long i = tid; i < n; i += KNN_THREADS) {
-            const unsigned long long v = c[i];
-            m = knn_min(m, v >= lower ? v : KNN_NONE);
-        }
-        m = knn_block_min(m, red[r & 1]);
-        if (tid == 0) knn_emit(m, idx, dist, q * k + r);
-        lower = m == KNN_NONE ? KNN_NONE : m + 1;
-    }
-}
-
 bool knn_shape_ok(int64_t N, int Q, int k) { return k >= 1 && k <= KNN_MAX_K && N >= k && N <= 0x7fffffffll && Q >= 0; }
 
 long long knn_tiles(int64_t N) { return (N + KNN_TILE - 1) / KNN_TILE; }
@@ -190,7 +142,7 @@ int vf_camera_knn_f32(const float* db, int64_t N, const float* queries, int Q, i
     hipLaunchKernelGGL(camera_knn_tile_kernel, dim3((unsigned)ntiles, (unsigned)qgroups), dim3(KNN_THREADS), 0, s, db, (long long)N, queries,
                        Q, k, pos_weight, (int)ntiles, cand, idx, dist);
     if (ntiles > 1)
-        hipLaunchKernelGGL(camera_knn_merge_kernel, dim3((unsigned)Q), dim3(KNN_THREADS), 0, s, cand, ntiles * k, k, idx, dist);
+        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)Q), dim3(KNN_THREADS), 0, s, cand, ntiles * k, k, idx, dist);
     return vf_last_status();
 }
 

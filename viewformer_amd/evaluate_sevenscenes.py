@@ -92,6 +92,31 @@ def load_image_match_map(image_match_map_filepath):
     return top_map
 
 
+def build_image_match_map(bank, queries, top_n: int, window: int = 0, batch_size: int = 64):
+    """The match map the reference reads from an outside retrieval system's file (:71-77), made from the bank itself: ``queries`` yields
+    the ``(frames uint8 [1,H,W,3], camera, file)`` items ``evaluate_scene`` takes; -> {file + '.color.png': [the ``top_n`` bank file
+    names that look most like the query, nearest first]} (``SceneBank.similar``: the code distance of ``ops.code_knn`` with ``window``),
+    ``batch_size`` queries per search.  What ``evaluate_scene(match_map=...)`` and ``load_image_match_map`` use."""
+    match_map = {}
+    for batch in _batched(queries, batch_size):
+        frames = torch.cat([torch.as_tensor(f) for f, _, _ in batch])                          # [B,H,W,3]
+        idx = bank.similar(images=frames, k=top_n, window=window).cpu().tolist()
+        for (_, _, file), row in zip(batch, idx):
+            match_map[file + '.color.png'] = [bank.files[i] for i in row]
+    return match_map
+
+
+def save_image_match_map(path, match_map):
+    """write ``match_map`` in the reference's text format, ``<query file> <matched file>`` per line, matches in list order:
+    ``load_image_match_map(path)`` returns an equal mapping"""
+    with open(path, 'w') as f:
+        for query, matches in match_map.items():
+            for m in matches:
+                if len(query.split()) != 1 or len(m.split()) != 1:
+                    raise ValueError(f'file names with white space cannot be written to a match map: {query!r} {m!r}')
+                f.write(f'{query} {m}\n')
+
+
 def draw_fill_indices(bank, count: int, rng=_random):
     """``random.sample(scene_lookup.files, count)`` (:191,:240) as bank indices, drawn on the host"""
     return [bank.index(x) for x in rng.sample(bank.files, count)]

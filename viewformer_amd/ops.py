@@ -1034,6 +1034,73 @@ def camera_knn(db, queries, k, pos_weight=0.3, return_dist=False):
     return (idx, dist) if return_dist else idx
 
 
+def codebook_distances(E, D, K):
+    """The distance table of a codebook (vf_codebook_dist_table_f32): ``E`` feature-major [D][ld >= K] fp32 on the GPU, as ``VQGAN._E``
+    holds it -> fp32 [K,K], T[a][b] = ||e_a - e_b||^2 summed over the features in order: exactly symmetric, exactly 0 on the diagonal.
+    One launch on the current stream, no synchronisation."""
+    D, K = int(D), int(K)
+    if not isinstance(E, torch.Tensor) or E.dim() != 2 or not E.is_cuda or E.dtype != torch.float32:
+        raise ValueError('codebook_distances: a 2-D fp32 codebook [D][K] on the GPU expected')
+    if E.shape[0] != D or E.shape[1] < K or K < 1 or D < 1 or E.stride(1) != 1 or (D > 1 and E.stride(0) < K):
+        raise ValueError(f'codebook_distances: E [D = {D}][>= K = {K}] with unit column stride expected, got {tuple(E.shape)} '
+                         f'(strides {tuple(E.stride())})')
+    table = torch.empty((K, K), dtype=torch.float32, device=E.device)
+    check(_lib.load().vf_codebook_dist_table_f32(_p(E), D, K, E.stride(0) if D > 1 else max(E.stride(0), K), _p(table), _stream()),
+          'vf_codebook_dist_table_f32')
+    return table
+
+
+def _code_rows(x, name):
+    """int32 code maps [n,t,t] or [n,t*t] on the GPU (rows may be strided) -> (the tensor, n, t*t, row stride)"""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or x.dtype != torch.int32:
+        raise ValueError(f'code_knn: {name} must be an int32 tensor [n,t,t] or [n,t*t]')
+    if x.dim() == 3:
+        if x.shape[1] != x.shape[2]:
+            raise ValueError(f'code_knn: {name} {tuple(x.shape)} is not a batch of square code maps')
+        x = x.reshape(x.shape[0], -1)
+    if x.shape[1] < 1:
+        raise ValueError(f'code_knn: {name} {tuple(x.shape)} holds no codes')
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x, x.shape[0], x.shape[1], (x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1]))
+
+
+def code_knn(db_codes, query_codes, table, k, window=0, exclude=None, return_dist=False):
+    """For each query code map the ``k`` maps of ``db_codes`` nearest in the windowed one-sided Chamfer distance over ``table``
+    (``codebook_distances``; vf_code_knn_f32): sum over the grid positions p of the smallest table[q[p]][m[p']] over the positions p'
+    within ``window`` tokens of p.  ``window=0``: the squared L2 distance of the two quantised latent maps.  ``db_codes`` int32 [N,t,t]
+    or [N,t*t], ``query_codes`` likewise [Q,...] (on the GPU), ``exclude``: None or one database row per query (int [Q], -1: none) that
+    the query must not return (a leave-one-out search of a bank against itself).  -> idx int32 [Q,k] ascending, ties to the lowest index;
+    with ``return_dist`` also the distances fp32 [Q,k].  1 <= k <= 32, k <= N (N - 1 with ``exclude``), t <= 16, 0 <= window <= t - 1.
+    One or two launches on the current stream, no synchronisation; a query's row does not depend on the other queries of the call."""
+    db, N, P, ld_db = _code_rows(db_codes, 'db_codes')
+    qs, Q, Pq, ld_q = _code_rows(query_codes, 'query_codes')
+    t = int(round(P ** 0.5))
+    if t * t != P or Pq != P:
+        raise ValueError(f'code_knn: {P} and {Pq} codes per row: one square grid expected')
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[0] != table.shape[1] or table.dtype != torch.float32:
+        raise ValueError('code_knn: table must be a square fp32 tensor [K,K]')
+    if not (db.is_cuda and qs.is_cuda and table.is_cuda) or not db.device == qs.device == table.device:
+        raise ValueError('code_knn: db_codes, query_codes and table must live on one GPU (no CPU fallback for the hot path)')
+    table = table.contiguous()
+    k, window = int(k), int(window)
+    if exclude is not None:
+        exclude = torch.as_tensor(exclude)
+        if exclude.numel() != Q or exclude.is_floating_point():
+            raise ValueError(f'code_knn: exclude must hold one database row per query ({Q}), got {tuple(exclude.shape)} {exclude.dtype}')
+        exclude = exclude.reshape(Q).to(device=db.device, dtype=torch.int32).contiguous()
+    if not 1 <= k <= min(32, N - (exclude is not None)) or not 0 <= window <= t - 1 or t > 16 or not 1 <= table.shape[0] <= 4096:
+        raise ValueError(f'code_knn: k = {k} (at most 32) of N = {N} rows{" less the excluded one" if exclude is not None else ""}, '
+                         f'window = {window} on a {t} x {t} grid (at most 16 x 16), {table.shape[0]} codes (at most 4096)')
+    idx = torch.empty((Q, k), dtype=torch.int32, device=db.device)
+    dist = torch.empty((Q, k), dtype=torch.float32, device=db.device) if return_dist else None
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.vf_code_knn_workspace_bytes(N, Q, k)), 8), dtype=torch.uint8, device=db.device)
+    check(lib.vf_code_knn_f32(_p(db), N, ld_db, _p(qs), Q, ld_q, t, _p(table), table.shape[0], window, _p(exclude), k, _p(idx), _p(dist),
+                              _p(ws), _stream()), 'vf_code_knn_f32')
+    return (idx, dist) if return_dist else idx
+
+
 def pose_tail_supported(K, L):
     """shapes vf_pose_tail_f32 takes: K features per row (a multiple of 4, at most 2048), L tokens per view (at most 256)"""
     return K % 4 == 0 and 4 <= K <= 2048 and 1 <= L <= 256

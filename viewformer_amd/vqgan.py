@@ -223,11 +223,21 @@ class VQGAN:
         conv('post_quant_conv')
         self._E = dev_t('quantize.embeddings')                      # [D][Kc]
         self._E_packed, self._e_sq = ops.vq_pack_codebook(self._E)
+        self._code_dist = None                                      # code_distances() belongs to the weights it was made from
         # the filtered lookup (fp16 candidate filter + exact re-rank: identical indices, ~10x less matrix time) where its shape
         # rules hold; the exact f32-MFMA kernel otherwise.  ``lookup='exact'`` forces the latter (tests cross-check the two).
         self._E_filter = (ops.vq_filter_pack(self._E) if self.lookup == 'filter' and ops.vq_filter_supported(*self._E.shape)
                           else None)
         torch.cuda.synchronize(dev)
+
+    _code_dist = None
+
+    def code_distances(self):
+        """fp32 [n_embed, n_embed]: the squared distance between the embeddings of every two codes (ops.codebook_distances), the table
+        ops.code_knn and SceneBank.similar search with.  Made on first use, dropped when the weights are replaced."""
+        if self._code_dist is None:
+            self._code_dist = ops.codebook_distances(self._E, self.config.embed_dim, self.config.n_embed)
+        return self._code_dist
 
     # ------------------------------------------------------------------ building blocks (NHWC rows)
     def _gn_part(self, cout, n, Ho, Wo, device):
