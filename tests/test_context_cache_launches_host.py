@@ -57,28 +57,31 @@ def _sample_rows(lg, rows, n, n_samples=1, want=('idx', 'logp'), **kw):
     return {k: full[k] for k in want}
 
 
+def host_records(m, shapes, tensors=True):
+    """``m._dense`` and ``m._head`` for layers of ``shapes`` = {name: (k, n)} without an upload: records that hold no packing (every
+    launch that would read one is a recorder's), with zero weights and biases, or none where the caller binds its own"""
+    from viewformer_amd.migt import _Dense
+    for name, (k, n) in shapes.items():
+        m._dense[name] = _Dense(k, n, torch.zeros(k, n), torch.zeros(n)) if tensors else _Dense(k, n)
+    m._head = _Dense(m.config.d_model, m.config.n_embeddings)
+
+
 def _model(monkeypatch, rec, arm):
     """the host model of tests/test_fork_host.py with fake weights, every launch a recorder"""
     from viewformer_amd import ops
     from viewformer_amd.config import MIGTConfig
-    from viewformer_amd.migt import MIGT, _Dense
+    from viewformer_amd.migt import MIGT
     m = MIGT(MIGTConfig(n_embeddings=NE, n_head=H, d_model=D, n_layer=NL, token_image_size=8, sequence_size=4), precision=arm)
     m.device, m._sd_host = torch.device('cpu'), {}
     lp = arm == 'bf16'
     m._act_dtypes = lambda: (lp, lp)
-
-    def dense(name, k, n):
-        d = _Dense()
-        d.k, d.n, d.w_raw, d.bias, d.wp, d.wp16, d.wp6 = k, n, torch.zeros(k, n), torch.zeros(n), None, None, None
-        m._dense[name] = d
-    dense('pose_embedding.c_fc', 7, 4 * D)
-    dense('pose_embedding.c_proj', 4 * D, D)
+    shapes = {'pose_embedding.c_fc': (7, 4 * D), 'pose_embedding.c_proj': (4 * D, D)}
     for i in range(NL):
-        dense(f'h.{i}.attn.c_attn', D, 3 * D); dense(f'h.{i}.attn.c_proj', D, D)
-        dense(f'h.{i}.mlp.c_fc', D, 4 * D); dense(f'h.{i}.mlp.c_proj', 4 * D, D)
+        shapes.update({f'h.{i}.attn.c_attn': (D, 3 * D), f'h.{i}.attn.c_proj': (D, D), f'h.{i}.mlp.c_fc': (D, 4 * D), f'h.{i}.mlp.c_proj': (4 * D, D)})
         m._ln[f'h.{i}.ln_1'] = (torch.zeros(D), torch.zeros(D)); m._ln[f'h.{i}.ln_2'] = (torch.zeros(D), torch.zeros(D))
+    host_records(m, shapes)
     m._ln['ln_f'] = (torch.zeros(D), torch.zeros(D))
-    m._wte, m._wpe, m._lm_head = torch.zeros(NE + 2, D), torch.zeros(L, D), torch.zeros(NE, D)
+    m._wte, m._wpe, m._head.packed['f32'] = torch.zeros(NE + 2, D), torch.zeros(L, D), torch.zeros(NE, D)
     names = {id(d): n for n, d in m._dense.items()}
     m._dense_launch = rec.wrap('_dense_launch')
     m._dense_launch = (lambda f: lambda x, d, *a, **k: f(x, names[id(d)], *a, **k))(m._dense_launch)
@@ -95,6 +98,8 @@ def _model(monkeypatch, rec, arm):
         stubs[name] = lambda *a, **k: None
     for name, fn in stubs.items():
         monkeypatch.setattr(ops, name, rec.wrap(name, fn))
+    igemm = ops.igemm                                          # an arm keyword left out is that keyword passed as False: the same launch
+    monkeypatch.setattr(ops, 'igemm', lambda *a, **k: igemm(*a, **dict(dict(bf16=False, x6=False, x3h=False), **k)))
     return m
 
 

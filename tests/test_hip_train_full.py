@@ -78,7 +78,7 @@ def test_full_size_step_is_finite_deterministic_and_bf16_tracks_the_fp32_arm(dev
         assert float(tr32.g(n).abs().max()) > 0 or n in zero_ok, n
 
     tr16 = _trainer(cfg, dev, 'bf16')
-    assert any(dn.wp16 is not None for dn in tr16.model._dense.values()) and len(tr16.wpT16) > 0
+    assert any('bf16' in dn.packed and 'bf16' in dn.packed_T for dn in tr16.model._dense.values())
     mb = tr16.train_step(poses, tokens, reduce_gradients=False, apply_update=False)
     assert abs(float(mb['loss']) - float(m1['loss'])) < 2e-2 * max(1.0, abs(float(m1['loss'])))
     worst = ('', 0.0)

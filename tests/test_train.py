@@ -491,7 +491,7 @@ def test_bf16_training_step_gradients_within_stated_tolerance(dev):
     weights, attention, normalisation, losses and optimizer and runs the dense GEMMs on bf16 MFMA"""
     from oracle import train_oracle as to
     cfg, sd, tokens, poses, tr = _setup(True, dev, precision='bf16')
-    assert any(dn.wp16 is not None for dn in tr.model._dense.values()) and len(tr.wpT16) > 0      # the bf16 path really runs
+    assert any('bf16' in dn.packed and 'bf16' in dn.packed_T for dn in tr.model._dense.values())      # the bf16 path really runs
     tr.step_count = 3
     metrics = tr.train_step(poses, tokens, reduce_gradients=False, apply_update=False)
     grads, ref_metrics = to.gradients(sd, cfg, poses, tokens, step=3)
@@ -1120,7 +1120,7 @@ def test_bf16_arm_lm_head_backward_uses_current_weights_when_rows_are_not_a_mult
     _, cams = synthetic_scene_batch(B, S, 8, 7)
     poses = mg.normalize_cameras(mg.to_relative_cameras(torch.from_numpy(cams))[0])
     tr = MIGTTrainer(MIGT(cfg, precision='bf16').load_state_dict(sd).to(dev), warmup_steps=1)
-    assert tr._lm16 is not None and (B * S * 16) % 64 != 0         # bf16 LM-head packings exist, and this batch cannot use them
+    assert 'bf16' in tr._head.packed and 'bf16' in tr._head.packed_T and (B * S * 16) % 64 != 0         # bf16 LM-head packings exist, and this batch cannot use them
     for _ in range(3):
         tr.train_step(poses, tokens)                               # three updates (the first at warm-up lr 0; lr 2e-2: the weights really move)
     moved = (tr.state_dict()['wte.weight'].cpu() - torch.as_tensor(sd['wte.weight'])).abs().max().item()
@@ -1440,7 +1440,9 @@ def test_fused_optimizer_repack_leaves_the_same_trainer_state_bit_for_bit(dev):
         assert tr._pack16 is not None and tr._adam_pack is not None and 2 * tr._adam_pack[1] == len(tr._pack16_keep) >= 2 * (4 * cfg.n_layer + 1)
         assert tr._packs_fresh is False
         packs = [out for _, _, out in tr._pack16_keep]               # every layer weight both ways, the tied LM head both ways
-        assert {id(x) for x in packs} >= {id(x) for x in tr._lm16} | {id(dn.wp16) for dn in tr.model._dense.values() if dn.wp16 is not None}
+        records = [tr._head] + list(tr.model._dense.values())
+        assert {id(x) for x in packs} >= {id(p['bf16']) for dn in records for p in (dn.packed, dn.packed_T) if 'bf16' in p}
+        assert 'bf16' in tr._head.packed and 'bf16' in tr._head.packed_T
         res.append([tr.flat_p.clone(), tr.flat_m.clone(), tr.flat_v.clone(), torch.stack(losses)] + [x.clone() for x in packs])
     assert len(res[0]) == len(res[1])
     for a, b in zip(*res):

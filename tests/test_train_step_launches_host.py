@@ -17,7 +17,7 @@ import os
 import pytest
 import torch
 
-from test_context_cache_launches_host import Recorder, digest
+from test_context_cache_launches_host import Recorder, digest, host_records
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'train_step_launches.json')
 D, H, NE, NL = 256, 4, 256, 2            # the smallest model at which every plan field can be true (256-wide tiles, 64-wide heads)
@@ -152,21 +152,17 @@ def _patch(monkeypatch, rec):
 def _trainer(rec, precision, NS, L, cfg_kw, attrs):
     """a host model with the generated weights' shapes, every launch a recorder, and its trainer"""
     from viewformer_amd.config import MIGTConfig
-    from viewformer_amd.migt import MIGT, _Dense
+    from viewformer_amd.migt import MIGT
     from viewformer_amd.train import MIGTTrainer
     from viewformer_amd.weights import make_migt_weights
     cfg = MIGTConfig(**dict(dict(n_embeddings=NE, n_head=H, d_model=D, n_layer=NL, token_image_size=int(L ** 0.5), sequence_size=4, n_loss_skip=1,
                                  dropout=0.0, localization_weight='1' if NS == 3 else '0'), **cfg_kw))
     m = MIGT(cfg, precision=precision).load_state_dict(make_migt_weights(cfg))
     m.device = torch.device('cpu')
+    host_records(m, {k[:-7]: m._sd_host[k].shape for k in m.expected_keys() if k.endswith('.weight') and k != 'wte.weight'}, tensors=False)
     for k in m.expected_keys():
-        if k.endswith('.weight') and k != 'wte.weight':
-            d = _Dense()
-            (d.k, d.n), d.w_raw, d.bias, d.wp, d.wp16, d.wp6 = m._sd_host[k].shape, None, None, None, None, None
-            m._dense[k[:-7]] = d
-        elif k.endswith('.gamma'):
+        if k.endswith('.gamma'):
             m._ln[k[:-6]] = None
-    m._lm_head = None
     m._gemm = rec.wrap('_gemm', lambda x, name, M, epilogue=None, res=None, out_bf16=False: _f(M, m._dense[name].n, dtype=_b16(out_bf16)))
     tr = MIGTTrainer(m)
     for k, v in attrs.items():

@@ -27,8 +27,22 @@ from .config import MIGTConfig
 from .context_cache import ContextCache, GrowingKVCache, GrowingE4M3Cache, PrefillSink      # noqa: F401  (tests and tools import ContextCache from here)
 
 
+ARMS = ('bf16', 'x3h', 'x6', 'f32')      # a dense launch's arithmetic (ops.ARM_KW), fastest first
+
+
 class _Dense:
-    __slots__ = ('wp', 'wp16', 'wp6', 'bias', 'k', 'n', 'w_raw')
+    """one dense layer [k] -> [n]: raw weight, bias, and its packings keyed by arm — ``packed`` for x @ W, ``packed_T`` for dy @ W^T
+    (``w_raw_T``: the unpacked transpose, _pose_embed_bwd).  The caches live and die with the record: new weights, new records."""
+    __slots__ = ('k', 'n', 'bias', 'w_raw', 'packed', 'packed_T', 'w_raw_T')
+
+    def __init__(self, k, n, w_raw=None, bias=None):
+        self.k, self.n, self.w_raw, self.bias = k, n, w_raw, bias
+        self.packed, self.packed_T, self.w_raw_T = {}, {}, None
+
+
+def dense_arm(d):
+    """the arm of a forward launch of record ``d``: the fastest it holds a packing for"""
+    return next(a for a in ARMS if a in d.packed)
 
 
 class MIGT:
@@ -41,7 +55,9 @@ class MIGT:
         ``precision='bf16'``: the dense layers (c_attn, c_proj, MLP, LM head, pose MLPs) run on the bf16-MFMA arm with
         fp32 activations / accumulation, and the attention contractions (q.k^T, p.v) on bf16 MFMA with an fp32 softmax;
         LayerNorm, the residual stream and the arg-max stay fp32.
-        Logits are then tolerance-bounded (tests state the bound), as the north star allows for the transformer."""
+        Logits are then tolerance-bounded (tests state the bound), as the north star allows for the transformer.
+        ``_upload`` decides which arms a layer (``_dense[name]``) and the tied LM head (``_head``) keep a packing for; ``dense_arm``
+        picks a launch's arm from them, and nothing else does."""
         assert precision in ('f32', 'bf16') and dense_arith in ('f32', 'x6', 'x3h') and attention in (None, 'bf16', 'fp8')
         if attention is not None and precision != 'bf16':
             raise ValueError("attention='bf16' / 'fp8' belong to the tolerance arm: use precision='bf16'")
@@ -63,7 +79,6 @@ class MIGT:
         self.skip_masked = skip_masked
         self._sd_host = None
         self._dense = {}
-        self._dense_t = {}
         self._ln = {}
         self._weights_version = 0                             # counts uploads: a ContextCache is tied to the weights that filled it
 
@@ -135,29 +150,22 @@ class MIGT:
         def dev_t(name):
             return torch.from_numpy(h[name]).to(dev, torch.float32).contiguous()
 
+        fast = 'bf16' if self.precision == 'bf16' else self.dense_arith if self.dense_arith != 'f32' else None
+        arms = lambda native, wide: ('f32',) * native + (fast,) * bool(fast and wide)      # noqa: E731  (native first: the order they are packed in)
+
         def dense(name, pack=True):
-            d = _Dense()
             w = dev_t(name + '.weight')
-            d.k, d.n = w.shape
-            d.bias = dev_t(name + '.bias')
-            d.w_raw = w
-            d.wp = ops.pack_dense_kn(w) if (pack and d.k % 32 == 0) else None
-            d.wp16 = ops.pack_dense_kn_bf16(w) if (self.precision == 'bf16' and pack and d.k % 64 == 0 and d.n >= 64) else None
-            split = d.wp16 is None and self.dense_arith in ('x6', 'x3h') and pack and d.k % 64 == 0 and d.n >= 64
-            # the packing's dtype names the arithmetic: bf16 planes = x6, f16 planes = x3h (_dense_launch)
-            d.wp6 = (ops.pack_dense_kn_x3h(w) if self.dense_arith == 'x3h' else ops.pack_dense_kn_x6(w)) if split else None
-            self._dense[name] = d
+            d = self._dense[name] = _Dense(*w.shape, w, dev_t(name + '.bias'))
+            d.packed = {a: ops.pack_dense(a, w) for a in arms(d.k % 32 == 0, d.k % 64 == 0 and d.n >= 64) if pack}
 
         def ln(name):
             self._ln[name] = (dev_t(name + '.gamma'), dev_t(name + '.beta'))
 
         self._wte = dev_t('wte.weight')
         self._wpe = dev_t('wpe.embeddings')
-        self._lm_head = ops.pack_dense_nk(self._wte, n_rows=c.n_embeddings)    # logits sliced to n_embeddings (migt.py:417)
-        self._lm_head16 = (ops.pack_dense_nk_bf16(self._wte, n_rows=c.n_embeddings)
-                           if self.precision == 'bf16' and c.d_model % 64 == 0 else None)
-        self._lm_head6 = ((ops.pack_dense_nk_x3h if self.dense_arith == 'x3h' else ops.pack_dense_nk_x6)(self._wte, n_rows=c.n_embeddings)
-                          if self._lm_head16 is None and self.dense_arith in ('x6', 'x3h') and c.d_model % 64 == 0 else None)
+        # the tied LM head as a layer d_model -> n_embeddings whose weight lies transposed: logits sliced to n_embeddings (migt.py:417)
+        self._head = _Dense(c.d_model, c.n_embeddings, self._wte[:c.n_embeddings])
+        self._head.packed = {a: ops.pack_dense(a, self._wte, True, c.n_embeddings) for a in arms(True, c.d_model % 64 == 0)}
         dense('pose_embedding.c_fc', pack=False)
         dense('pose_embedding.c_proj')
         dense('pose_criterion.pose_classifier.c_fc')
@@ -167,7 +175,6 @@ class MIGT:
             for p in ('attn.c_attn', 'attn.c_proj', 'mlp.c_fc', 'mlp.c_proj'):
                 dense(f'h.{i}.{p}')
         ln('ln_f')
-        self._dense_t = {}                                                   # transposed packs (_dense_T) belong to the weights they were made from
         self._weights_version += 1
         torch.cuda.synchronize(dev)
 
@@ -180,20 +187,15 @@ class MIGT:
 
     @staticmethod
     def _dense_launch(x, d, M, out, res=None, epilogue=ops.EPI_NONE):
-        """one dense layer on the arm its packing selects: bf16 (tolerance arm) > x6 (fp32-equivalent) > native f32 MFMA"""
-        bf16, x6 = d.wp16 is not None, d.wp16 is None and getattr(d, 'wp6', None) is not None
-        x3h = x6 and d.wp6.dtype == torch.float16
-        ops.igemm(x, d.wp16 if bf16 else d.wp6 if x6 else d.wp, M, d.k, d.n, out, bias=d.bias, res=res, epilogue=epilogue,
-                  bf16=bf16, x6=x6 and not x3h, x3h=x3h, a16=x.dtype == torch.bfloat16, o16=out.dtype == torch.bfloat16)
+        """one dense layer on the arm ``dense_arm`` picks: bf16 (tolerance arm) > x3h, x6 (fp32-equivalent) > native f32 MFMA"""
+        arm = dense_arm(d)
+        ops.igemm(x, d.packed[arm], M, d.k, d.n, out, bias=d.bias, res=res, epilogue=epilogue, **ops.ARM_KW[arm], a16=x.dtype == torch.bfloat16,
+                  o16=out.dtype == torch.bfloat16)
 
     def _lm(self, h, M, out):
         """tied LM head: logits = h @ wte[:n_embeddings]^T  (SharedEmbeddings._linear, migt.py:51-56,417)"""
-        c = self.config
-        bf16 = getattr(self, '_lm_head16', None) is not None
-        x6 = not bf16 and getattr(self, '_lm_head6', None) is not None
-        x3h = x6 and self._lm_head6.dtype == torch.float16
-        ops.igemm(h, self._lm_head16 if bf16 else self._lm_head6 if x6 else self._lm_head, M, c.d_model, c.n_embeddings, out,
-                  bf16=bf16, x6=x6 and not x3h, x3h=x3h)
+        d, arm = self._head, dense_arm(self._head)
+        ops.igemm(h, d.packed[arm], M, d.k, d.n, out, **ops.ARM_KW[arm])
         return out
 
     def _lm_argmax(self, h, M):
@@ -201,9 +203,9 @@ class MIGT:
         ``tf.argmax(logits, -1)`` would give (evaluate_transformer.py:123), or None where the fused form does not apply (fp32 arm,
         odd shapes) — callers then compute the logits and call ops.argmax_rows."""
         c = self.config
-        if getattr(self, '_lm_head16', None) is None or not ops.lmhead_argmax_supported(c.d_model, c.n_embeddings):
+        if 'bf16' not in self._head.packed or not ops.lmhead_argmax_supported(c.d_model, c.n_embeddings):
             return None
-        return ops.lmhead_argmax_bf16(h, self._lm_head16, M, c.d_model, c.n_embeddings)
+        return ops.lmhead_argmax_bf16(h, self._head.packed['bf16'], M, c.d_model, c.n_embeddings)
 
     def _lm_score(self, hf, M, target=None, fused: bool = False, want=ops.SCORE_OUTPUTS):
         """soft-max statistics of the tied LM head per row (ops.SCORE_OUTPUTS: first arg-max, its logit, log-sum-exp, the logit of
@@ -213,8 +215,8 @@ class MIGT:
         streams the whole packed wte), hence not the default; on every other arm and shape ``fused=True`` takes the default route.  There
         is no third route."""
         c = self.config
-        if fused and getattr(self, '_lm_head16', None) is not None and ops.lmhead_score_supported(c.d_model, c.n_embeddings):
-            return ops.lmhead_score_bf16(hf, self._lm_head16, M, c.d_model, c.n_embeddings, target=target, want=want)
+        if fused and 'bf16' in self._head.packed and ops.lmhead_score_supported(c.d_model, c.n_embeddings):
+            return ops.lmhead_score_bf16(hf, self._head.packed['bf16'], M, c.d_model, c.n_embeddings, target=target, want=want)
         lg = torch.empty((M, c.n_embeddings), dtype=torch.float32, device=hf.device)
         self._lm(hf, M, lg)                                                  # migt.py:417
         return ops.logits_score(lg, M, c.n_embeddings, target=target, want=want)
@@ -243,7 +245,7 @@ class MIGT:
         d = c.d_model
         l0 = self._dense['h.0.mlp.c_proj'] if c.n_layer else None
         act16 = (self.precision == 'bf16' and self.bf16_activations and d % 128 == 0 and l0 is not None and l0.k % 128 == 0
-                 and all(self._dense[f'h.{i}.{n}'].wp16 is not None for i in range(c.n_layer)
+                 and all('bf16' in self._dense[f'h.{i}.{n}'].packed for i in range(c.n_layer)
                          for n in ('attn.c_attn', 'attn.c_proj', 'mlp.c_fc', 'mlp.c_proj')))
         # the fused c_attn output is bf16 too (bit-identical downstream: the attention kernel rounds fp32 q/k/v to bf16 on load): half
         # the bytes written by the GEMM and read by the attention, whose LDS-DMA kernel (attention_dma.hip) takes bf16 tiles straight
@@ -543,25 +545,17 @@ class MIGT:
         """the native-fp32 TRANSPOSED pack of a dense layer, for dx = dy @ W^T on ``ops.igemm`` (MIGTTrainer._linear_dx's last branch), made
         on first use and kept until the weights are replaced; ``'wte'``: ``wte[:n_embeddings]`` as an [n_embeddings -> d] layer, the
         transpose of the tied LM head"""
-        t = self._dense_t.get(name)
-        if t is None:
-            if name == 'wte':
-                c = self.config
-                t = ops.pack(self._wte, c.n_embeddings, c.d_model, 1, sk=c.d_model, sn=1, st=0)
-            else:
-                dn = self._dense[name]
-                t = ops.pack(dn.w_raw, dn.n, dn.k, 1, sk=1, sn=dn.n, st=0)
-            self._dense_t[name] = t
-        return t
+        dn = self._head if name == 'wte' else self._dense[name]
+        if 'f32' not in dn.packed_T:
+            w, sk, sn = (self._wte, dn.k, 1) if name == 'wte' else (dn.w_raw, 1, dn.n)          # (the head's weight lies transposed)
+            dn.packed_T['f32'] = ops.pack(w, dn.n, dn.k, 1, sk=sk, sn=sn, st=0)
+        return dn.packed_T['f32']
 
     def _linear_dx(self, name, dy, M, res=None):
         """dx [M, k] = dy [M, n] @ W^T (+ res) in native fp32, whatever the arm of the forward"""
-        if name == 'wte':
-            k, n = self.config.d_model, self.config.n_embeddings
-        else:
-            k, n = self._dense[name].k, self._dense[name].n
-        dx = torch.empty((M, k), dtype=torch.float32, device=dy.device)
-        ops.igemm(dy, self._dense_T(name), M, n, k, dx, res=res)
+        dn = self._head if name == 'wte' else self._dense[name]
+        dx = torch.empty((M, dn.k), dtype=torch.float32, device=dy.device)
+        ops.igemm(dy, self._dense_T(name), M, dn.n, dn.k, dx, res=res)
         return dx
 
     def _pose_embed_bwd(self, poses, dadd):
@@ -577,10 +571,9 @@ class MIGT:
         u = ops.dense_small_k(pin, fc.w_raw, fc.bias, R, 7, fc.n, gelu=False)
         du = T.gelu_bwd(u, self._linear_dx('pose_embedding.c_proj', dadd, R))
         if T.dense_small_n_supported(fc.n, fc.k):
-            wt = self._dense_t.get('pose_embedding.c_fc.T')
-            if wt is None:
-                wt = self._dense_t['pose_embedding.c_fc.T'] = T.transpose(fc.w_raw, fc.k, fc.n).view(fc.n, fc.k)
-            dpin = T.dense_small_n(du, wt, None, R, fc.n, fc.k)
+            if fc.w_raw_T is None:
+                fc.w_raw_T = T.transpose(fc.w_raw, fc.k, fc.n).view(fc.n, fc.k)
+            dpin = T.dense_small_n(du, fc.w_raw_T, None, R, fc.n, fc.k)
         else:
             dpin = self._linear_dx('pose_embedding.c_fc', du, R)
         # (a Python scalar: a constant built on the host would be a blocking copy, and a synchronise, in every pass)

@@ -234,6 +234,12 @@ def pack_dense_nk_arm(arm, w, n_rows=None):
     return {'f32': pack_dense_nk, 'x6': pack_dense_nk_x6, 'x3h': pack_dense_nk_x3h, 'bf16': pack_dense_nk_bf16}[arm](w, n_rows)
 
 
+def pack_dense(arm, w, transposed=False, n_rows=None):
+    """w [K][N] for x @ W, or ``transposed`` [N][K] (its first n_rows rows) for x @ W^T -> the packing igemm(**ARM_KW[arm]) reads"""
+    fn = globals()['pack_dense_' + ('nk' if transposed else 'kn') + ('' if arm == 'f32' else '_' + arm)]
+    return fn(w) if n_rows is None else fn(w, n_rows=n_rows)
+
+
 def gemm_bf16_splitk(x, w_packed, M, Cin, Cout, dst, splits, lda=None, accumulate=True):
     """dst[M][Cout] (+)= x @ W on the bf16 arm with the reduction split over ``splits`` slabs: the split-K of a weight-gradient GEMM
     (few output tiles, a reduction of tens of thousands of rows) expressed as a BATCHED launch of vf_gemm_bf16 — batch entry s

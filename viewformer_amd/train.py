@@ -41,7 +41,7 @@ from . import ops
 from . import train_ops as T
 from . import geometry
 from . import sharding
-from .migt import MIGT
+from .migt import MIGT, _Dense
 
 
 def parse_schedule(s, total_steps=None):
@@ -133,6 +133,16 @@ def site_mlp(i):
 def bf16_packed(precision, k, n):
     """the trainer's rule for a dense layer [k][n] with bf16 packings (MIGTTrainer.repack; it drops the model's other packings)"""
     return precision == 'bf16' and k % 128 == 0 and n % 128 == 0
+
+
+def train_arm(dn, M):
+    """the arm of a dense layer's backward launches (dW, dX) at M rows, from the packings repack left in its record: bf16 where both bf16
+    packings exist and M % 128 == 0; the split arm 'x6' where both split packings exist (the forward one may be 'x3h': activations
+    only) and M % 64 == 0; else native 'f32'.  (The forward launch takes migt.dense_arm(dn) at every M.)"""
+    if M % 128 == 0 and 'bf16' in dn.packed and 'bf16' in dn.packed_T:
+        return 'bf16'
+    split = M % 64 == 0 and 'x6' in dn.packed_T and ('x3h' in dn.packed or 'x6' in dn.packed)
+    return 'x6' if split else 'f32'
 
 
 def block_layer_shapes(cfg):
@@ -363,9 +373,7 @@ class MIGTTrainer:
     _adam_pack = None                 # descriptor range per transformer layer (_build_pack_tables)
     _layer_pack_ranges = None
     _packs_fresh = False              # apply_gradients' fused optimizer wrote the packings with the update: the next repack skips them
-    _lm16 = None                      # the tied LM head's two bf16 packings
-    lm_T = None                       # ... and its native transposed packing (_pack_lm_T)
-    _lm_T_stale = True
+    _lm_T_stale = True                # _head.packed_T['f32'] is not of the current weights (_pack_lm_T)
     _side_busy = False                # a weight-gradient GEMM is in flight on the 'side' stream (_join_side)
     _unset = frozenset()              # lazy_gradient_zero: the layer tensor pairs no kernel has written yet this step
     _layer_grad_keys = None
@@ -391,7 +399,7 @@ class MIGTTrainer:
         self.lr_offset = 0                           # WarmUp.offset (models/utils.py:337): begin_finetune() moves it
         self.lr_init, self.lr_total_steps = cfg.learning_rate, cfg.total_steps     # create_optimizer's arguments (train_transformer.py)
         self.loc_weight = parse_schedule(cfg.localization_weight, cfg.total_steps)
-        self.wpT, self.wpT6, self.wpT16 = {}, {}, {}     # transposed packings per dense layer: native f32, split (x6), bf16
+        self._head = _Dense(cfg.d_model, cfg.n_embeddings)   # the TRAINER's packings of the tied LM head (bf16 both ways, native transposed): the model's own head keeps the native one
         self._streams, self._nodecay = {}, {}            # _stream(name), _nodecay_table(a, b)
         self._layout()
         self._bind()
@@ -449,6 +457,7 @@ class MIGTTrainer:
         m._wte, m._wpe =self.p('wte.weight'), self.p('wpe.embeddings')
         for name, dn in m._dense.items():
             dn.w_raw, dn.bias = self.p(name + '.weight'), self.p(name + '.bias')
+        m._head.w_raw = m._wte[:self.cfg.n_embeddings]
         for name in list(m._ln):
             m._ln[name] = (self.p(name + '.gamma'), self.p(name + '.beta'))
         self.repack()
@@ -458,17 +467,14 @@ class MIGTTrainer:
         pose heads), and with ``dense_arith='x6'`` the fp32-equivalent split packings the dense layers actually run on —
         forward W, and W^T for dX (x6 GEMMs are ~1.8x the native ones; the packers are a few launches per layer).  ``early_layers_done``
         (apply_gradients): the transformer layers' bf16 packings were refreshed right after their early update"""
-        m, nE, d = self.model, self.cfg.n_embeddings, self.cfg.d_model
+        m, nE, d, th = self.model, self.cfg.n_embeddings, self.cfg.d_model, self._head
         bf16 = m.precision == 'bf16'          # the reference trains with --fp16 (mixed_float16): bf16 MFMA, fp32 master weights
-        x6 = m.dense_arith in ('x6', 'x3h') and not bf16
-        x3h = m.dense_arith == 'x3h'          # forward activations only; dX / dW (gradient magnitudes) stay on x6
-        m._lm_head16 = m._lm_head6 = None                   # the LM head / pose heads stay on the native kernel in training
+        split = None if bf16 or m.dense_arith == 'f32' else m.dense_arith     # 'x3h': forward activations only; dX / dW (gradient magnitudes) stay on x6
         lm16 = bf16 and self.bf16_lm_head and d % 256 == 0 and nE % 256 == 0
-        if lm16 and self._lm16 is None:
+        if lm16 and 'bf16' not in th.packed:
             self._pack16 = self._adam_pack = None                # (the LM-head packings join the descriptor table: rebuild it)
         if self._pack16 is not None and (not bf16 or any(
-                dn.wp16 is None or name not in self.wpT16 for name, dn in m._dense.items()
-                if dn.k % 128 == 0 and dn.n % 128 == 0)):
+                train_arm(dn, 128) != 'bf16' for dn in m._dense.values() if dn.k % 128 == 0 and dn.n % 128 == 0)):
             # the table holds raw pointers into packings that are gone (the arm was switched to f32 and back, or a layer lost its
             # buffers): never run it against them — rebuild from scratch below
             self._pack16 = self._pack16_keep = self._layer_pack_ranges = self._adam_pack = None
@@ -486,33 +492,34 @@ class MIGTTrainer:
         for name, dn in m._dense.items():
             k32 = dn.k % 32 == 0
             to16 = bf16_packed(m.precision, dn.k, dn.n)
-            to6 = x6 and k32 and dn.k % 64 == 0 and dn.n % 64 == 0
+            to6 = split is not None and k32 and dn.k % 64 == 0 and dn.n % 64 == 0
             # the native-f32 packings are refreshed only where no faster arm applies (they were 477 pack launches per step that nothing
             # read: the wide layers run on their bf16 / split packings); the transposed native packing of a wide layer is built on demand
-            # in _linear_dx for row counts its arm does not tile
-            dn.wp = ops.pack(dn.w_raw, dn.k, dn.n, 1, sk=dn.n, sn=1, st=0, out=dn.wp) if k32 and not (to16 or to6) else None    # forward: x @ W
+            # in _linear_dx for row counts its arm does not tile.  The record's dicts are replaced: what this rule does not keep is gone
+            old, old_T, w = dn.packed, dn.packed_T, dn.w_raw
+            dn.packed, dn.packed_T = {}, {}
+            if k32 and not (to16 or to6):                                                                     # forward: x @ W
+                dn.packed['f32'] = ops.pack(w, dn.k, dn.n, 1, sk=dn.n, sn=1, st=0, out=old.get('f32'))
             if dn.n % 32 == 0 and not (to16 or to6):                                                          # dX = dY @ W^T
-                self.wpT[name] = ops.pack(dn.w_raw, dn.n, dn.k, 1, sk=1, sn=dn.n, st=0, out=self.wpT.get(name))
-            else:
-                self.wpT.pop(name, None)
-            dn.wp6 = None
-            if not to16:
-                dn.wp16 = None
-            elif not tables:                                      # (with the tables: the buffers of the one-launch refresh above)
-                dn.wp16, self.wpT16[name] = ops.pack_dense_kn_bf16(dn.w_raw), ops.pack_dense_nk_bf16(dn.w_raw)
-                new += [(name, dn.w_raw, False, dn.wp16), (name, dn.w_raw, True, self.wpT16[name])]
+                dn.packed_T['f32'] = ops.pack(w, dn.n, dn.k, 1, sk=1, sn=dn.n, st=0, out=old_T.get('f32'))
+            if to16 and tables:                                   # (the buffers of the one-launch refresh above)
+                dn.packed['bf16'], dn.packed_T['bf16'] = old['bf16'], old_T['bf16']
+            elif to16:
+                dn.packed['bf16'], dn.packed_T['bf16'] = ops.pack_dense('bf16', w), ops.pack_dense('bf16', w, True)
+                new += [(name, w, False, dn.packed['bf16']), (name, w, True, dn.packed_T['bf16'])]
             if to6:
-                dn.wp6 = ops.pack_dense_kn_x3h(dn.w_raw) if x3h else ops.pack_dense_kn_x6(dn.w_raw)
-                self.wpT6[name] = ops.pack_dense_nk_x6(dn.w_raw)          # [K][N] read as the transposed [N][K] operand
+                dn.packed[split] = ops.pack_dense(split, w)
+                dn.packed_T['x6'] = ops.pack_dense('x6', w, True)             # [K][N] read as the transposed [N][K] operand
         if lm16 and not tables:                                      # tied LM head on the bf16 pipe: logits = h @ wte^T, dH = dlogits @ wte
-            head, first = m._wte[:nE], self._lm16 is None            # (not the first: the per-tensor refresh, one_launch_repack off)
-            self._lm16 = (ops.pack_dense_nk_bf16(head), ops.pack_dense_kn_bf16(head))
+            head, first = m._head.w_raw, 'bf16' not in th.packed     # (not the first: the per-tensor refresh, one_launch_repack off)
+            th.packed['bf16'], th.packed_T['bf16'] = ops.pack_dense('bf16', head, True), ops.pack_dense('bf16', head)
             if first:
-                new += [('wte', head, True, self._lm16[0]), ('wte', head, False, self._lm16[1])]
+                new += [('wte', head, True, th.packed['bf16']), ('wte', head, False, th.packed_T['bf16'])]
         if bf16 and not tables and new and self.one_launch_repack:
             self._build_pack_tables(new)
-        m._lm_head = ops.pack(m._wte, d, nE, 1, sk=1, sn=d, st=0, out=m._lm_head)                          # logits = h @ wte^T (kept fresh for
-        if not lm16:                                                                                      # whoever reads the model afterwards)
+        # the model's own head: the fresh native packing and nothing else (logits = h @ wte^T for whoever reads the model afterwards)
+        m._head.packed, m._head.packed_T = {'f32': ops.pack(m._wte, d, nE, 1, sk=1, sn=d, st=0, out=m._head.packed.get('f32'))}, {}
+        if not lm16:
             self._pack_lm_T()
         else:
             self._lm_T_stale = True           # the step's own predicate also needs M1 % 64 == 0: its fallback must re-pack from THESE weights
@@ -544,7 +551,7 @@ class MIGTTrainer:
     def _pack_lm_T(self):
         """the tied LM head's native transposed packing (dH = dlogits @ wte), from the current weights"""
         c = self.cfg
-        self.lm_T = ops.pack(self.model._wte, c.n_embeddings, c.d_model, 1, sk=c.d_model, sn=1, st=0, out=self.lm_T)
+        self._head.packed_T['f32'] = ops.pack(self.model._wte, c.n_embeddings, c.d_model, 1, sk=c.d_model, sn=1, st=0, out=self._head.packed_T.get('f32'))
         self._lm_T_stale = False
 
     def _nodecay_table(self, a, b):
@@ -575,7 +582,7 @@ class MIGTTrainer:
             return self._linear(x, name, M, res=res)
         if fused and x.dtype == torch.bfloat16:
             out = torch.empty((M, dn.n), dtype=torch.float32, device=x.device)
-            ops.igemm(x, dn.wp16, M, dn.k, dn.n, out, bias=dn.bias, res=res, bf16=True, a16=True, drop=drop)
+            ops.igemm(x, dn.packed['bf16'], M, dn.k, dn.n, out, bias=dn.bias, res=res, bf16=True, a16=True, drop=drop)
             return out
         y = self._linear(x, name, M)
         return T.dropout_add(y, drop[0], drop[1], drop[2], res=res, out=y, row0=drop[3])
@@ -591,7 +598,7 @@ class MIGTTrainer:
         """dW and db of y = x @ W + b into the layer's gradient pair; ``dx_follows``: the layer's dX GEMM is issued next"""
         dn = self.model._dense[name]
         K, N = dn.k, dn.n
-        bf16 = name in self.wpT16 and dn.wp16 is not None and M % 128 == 0
+        bf16 = (arm := train_arm(dn, M)) == 'bf16'
         first = self._first_write(name)                   # (lazy_gradient_zero: this layer's gradient pair holds last step's values, not zeros)
         gw, gb = self.g(name + '.weight'), self.g(name + '.bias')
         if bf16 and self.tn_weight_gradient and ops.gemm_tn_bf16_supported(x, M, K, N):
@@ -631,7 +638,7 @@ class MIGTTrainer:
                 ops.gemm_bf16_splitk(xt, ops.pack_dense_kn_bf16(dy), K, M, N, gw, splits, lda=Mp)
             else:
                 ops.igemm(xt, ops.pack_dense_kn_bf16(dy), K, M, N, gw, res=gw, lda=Mp, bf16=True)
-        elif name in self.wpT6 and dn.wp6 is not None and M % 64 == 0:
+        elif arm == 'x6':
             splits = max(1, min(16, 768 // tiles, M // 1024))
             if splits > 1 and (K * N) % 4 == 0:
                 ops.gemm_x6_splitk(xt, ops.pack_dense_kn_x6(dy), K, M, N, gw, splits, lda=Mp)
@@ -678,8 +685,7 @@ class MIGTTrainer:
         (save_gelu_derivative): that bf16 tensor holds gelu'(u) already"""
         dn = self.model._dense[name]
         K, N = dn.k, dn.n
-        x6 = name in self.wpT6 and dn.wp6 is not None and M % 64 == 0
-        bf16 = name in self.wpT16 and dn.wp16 is not None and M % 128 == 0
+        bf16 = (arm := train_arm(dn, M)) == 'bf16'
         if dx_bf16 and not (bf16 and res is None):
             raise RuntimeError('dx_bf16 needs the bf16 arm and no residual')
         dx = torch.empty((M, K), dtype=torch.bfloat16 if dx_bf16 else torch.float32, device=dy.device)
@@ -687,14 +693,14 @@ class MIGTTrainer:
             if not (bf16 and dx_bf16 and res is None):
                 raise RuntimeError('the fused GELU backward needs the bf16 arm, a bf16 result and no residual')
             u16 = gelu_bwd_u.dtype == torch.bfloat16
-            ops.igemm(dy, self.wpT16[name], M, N, K, dx, res=gelu_bwd_u, epilogue=ops.EPI_GELU_BWD, bf16=True, a16=dy.dtype == torch.bfloat16, o16=True,
+            ops.igemm(dy, dn.packed_T['bf16'], M, N, K, dx, res=gelu_bwd_u, epilogue=ops.EPI_GELU_BWD, bf16=True, a16=dy.dtype == torch.bfloat16, o16=True,
                       res16=u16, gelu_grad=u16 and u_is_derivative)
         elif bf16:
-            ops.igemm(dy, self.wpT16[name], M, N, K, dx, res=res, bf16=True, a16=dy.dtype == torch.bfloat16, o16=dx_bf16)   # (bf16 dY: the 256-tile kernel)
-        elif x6:
-            ops.igemm(dy, self.wpT6[name], M, N, K, dx, res=res, x6=True)
+            ops.igemm(dy, dn.packed_T['bf16'], M, N, K, dx, res=res, bf16=True, a16=dy.dtype == torch.bfloat16, o16=dx_bf16)   # (bf16 dY: the 256-tile kernel)
+        elif arm == 'x6':
+            ops.igemm(dy, dn.packed_T['x6'], M, N, K, dx, res=res, x6=True)
         else:
-            wpT = self.wpT.get(name)
+            wpT = dn.packed_T.get('f32')
             if wpT is None:                                                          # (a wide layer at a row count its arm does not tile)
                 wpT = ops.pack(dn.w_raw, dn.n, dn.k, 1, sk=1, sn=dn.n, st=0)
             ops.igemm(dy, wpT, M, N, K, dx, res=res)
@@ -919,7 +925,7 @@ class MIGTTrainer:
             u = torch.empty((Mi, dn.n), dtype=torch.bfloat16 if plan.u16 else torch.float32, device=dev)
             f = torch.empty((Mi, dn.n), dtype=torch.bfloat16, device=dev)
             u_deriv = plan.gelu_derivative                                            # (`u` then holds gelu'(u): see save_gelu_derivative)
-            ops.igemm(n2, dn.wp16, Mi, dn.k, dn.n, u, bias=dn.bias, epilogue=ops.EPI_GELU_DUAL, bf16=True, a16=True, o16=plan.u16, out_aux=f,
+            ops.igemm(n2, dn.packed['bf16'], Mi, dn.k, dn.n, u, bias=dn.bias, epilogue=ops.EPI_GELU_DUAL, bf16=True, a16=True, o16=plan.u16, out_aux=f,
                       gelu_grad=u_deriv)
         else:
             u = self._linear(n2, p + '.mlp.c_fc', Mi)
@@ -938,11 +944,11 @@ class MIGTTrainer:
         denom = float((S - skip) * L * B)
         hmask = hf[:, 1 - so].contiguous().view(M1, d)
         logits = torch.empty((M1, nE), dtype=torch.float32, device=dev)
-        lm16 = self._lm16 is not None and m.precision == 'bf16' and self.bf16_lm_head and M1 % 64 == 0
+        lm16 = 'bf16' in self._head.packed and m.precision == 'bf16' and self.bf16_lm_head and M1 % 64 == 0
         if lm16:
-            ops.igemm(hmask, self._lm16[0], M1, d, nE, logits, bf16=True)
+            ops.igemm(hmask, self._head.packed['bf16'], M1, d, nE, logits, bf16=True)
         else:
-            ops.igemm(hmask, m._lm_head, M1, d, nE, logits)
+            ops.igemm(hmask, m._head.packed['f32'], M1, d, nE, logits)
         tgt = tok.reshape(M1).to(torch.int32).contiguous()
         w_ce = (view_ok * (c.image_generation_weight / denom)).contiguous()
         ce_rows, dlogits = T.softmax_ce(logits, tgt, w_ce, M1, nE, c.label_smoothing)        # :420-423
@@ -1011,13 +1017,13 @@ class MIGTTrainer:
         dhm = torch.empty((M1, d), dtype=torch.float32, device=dev)
         gwte = self.g('wte.weight')
         if heads.lm16:
-            ops.igemm(dlogits, self._lm16[1], M1, nE, d, dhm, bf16=True)
+            ops.igemm(dlogits, self._head.packed_T['bf16'], M1, nE, d, dhm, bf16=True)
             # dwte[:nE] = dlogits^T @ H straight from the row-major operands (the TN kernel: x = dlogits as bf16, dy = H)
             ops.gemm_tn_bf16(dlogits.to(torch.bfloat16), hmask, M1, nE, d, gwte[:nE], None)
         else:
             if self._lm_T_stale:              # (M1 % 64 != 0 in the bf16 arm: repack() skipped the native transposed packing — build it from the
                 self._pack_lm_T()             # CURRENT weights, every step: a packing cached from step 1 would be silently stale)
-            ops.igemm(dlogits, self.lm_T, M1, nE, d, dhm)
+            ops.igemm(dlogits, self._head.packed_T['f32'], M1, nE, d, dhm)
             M1p = (M1 + 31) // 32 * 32                                                # reduction length padded to the K stage (B * S * L = 48 at
             dlt = T.transpose(dlogits, M1, nE, ld_dst=M1p,                            # 16-token views and an odd B * S)
                               out=torch.zeros((1, nE, M1p), dtype=torch.float32, device=dev) if M1p != M1 else None)
