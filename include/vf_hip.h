@@ -281,8 +281,9 @@ int vf_attn_blockcausal_x6(const float* q, const float* k, const float* v, float
  * each prefix tile into LDS once for them; a query's result does not depend on N or on its position (bit-identical).
  *   vf_attn_prefix_bf16:  bf16 MFMA; in_bf16: q / k / v / kp / vp are bf16 (ld*, prefix_stride % 8) or fp32 (% 4); out_bf16 as above.
  *   vf_attn_prefix_f32eq: fp32-equivalent (x6 splitting as vf_attn_blockcausal_x6), fp32 everywhere.
- * L = 64 and dh = 64 (head dimension), C >= 1: anything else VF_ERR_UNSUPPORTED before any launch; NULL pointers, ld* < H * 64 or
- * misaligned: VF_ERR_BAD_ARG; B = 0 or N = 0: no-op, VF_OK. */
+ * L = 64 and dh = 64 (head dimension), C >= 1: anything else VF_ERR_UNSUPPORTED before any launch (C = 0 included; a negative B, N or C
+ * is VF_ERR_BAD_ARG); NULL pointers, ld* < H * 64, ld* or prefix_stride misaligned, prefix_stride < 0: VF_ERR_BAD_ARG; B = 0 or N = 0:
+ * no-op, VF_OK. */
 int vf_attn_prefix_bf16(const void* q, const void* k, const void* v, const void* kp, const void* vp, int in_bf16, void* out, int out_bf16,
                         int B, int H, int C, int N, int L, int dh, int ldq, int ldk, int ldv, int ldkp, int ldvp, int64_t prefix_stride,
                         int ldo, void* stream);
