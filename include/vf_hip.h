@@ -487,6 +487,31 @@ int vf_logits_score_f32(const float* logits, int64_t rows, int N, int64_t ld, co
  * order (one fp32 chain) and accuracy = the share of its rows with idx == target, [views] each.  One wave per view. */
 int vf_score_views_f32(const float* target_logit, const float* lse, const float* max_logit, const int64_t* idx, const int32_t* target,
                        int64_t views, int L, float* token_log_prob, float* confidence, float* log_likelihood, float* accuracy, void* stream);
+/* P photos against M cameras per scene from the M scored views alone (csrc/match_views.hip): a MASK view's logits do not depend on the
+ * photo, so the [B][M][P] matrix is a gather from M views' logits and a sum — what vf_score_views_f32 gives for one (view, photo) pair,
+ * for every pair.
+ *   logits   fp32 [B*M*L][ld], ld >= V; columns V..ld-1 are never read.  Row (b*M + m)*L + t is token t of camera m of scene b.
+ *   lse      fp32 [B*M*L], idx int64 [B*M*L]: the rows' log-sum-exp and first arg-max as vf_logits_score_f32 writes them; idx may be
+ *            NULL only when accuracy is NULL.
+ *   codes    int32; photo p of scene b starts at codes + b*codes_scene_stride + p*L.  codes_scene_stride == 0: one photo set shared by
+ *            all scenes; otherwise >= P*L.
+ *   log_likelihood fp32 [B][M][P] (camera-major, P fastest); accuracy NULL or fp32 [B][M][P].
+ * For every (b, m, p), with c_t = codes[b][p][t] and row_t = (b*M + m)*L + t:
+ *   x_t = (0 <= c_t < V) ? fsub_rn(logits[row_t][c_t], lse[row_t]) : -inf        (for a code outside [0, V) NOTHING is read from logits)
+ *   log_likelihood[b][m][p] = x_0 + x_1 + ... + x_{L-1} as ONE fp32 chain in token order: s = x_0; s = fadd_rn(s, x_t)
+ *   accuracy[b][m][p]       = (float)#{t : idx[row_t] == c_t} / (float)L
+ * — vf_score_views_f32's arithmetic on that pair; only where lse is -inf (a row of nothing but -inf) AND the code lies outside [0, V)
+ * do the two differ: x_t is -inf here, NaN there.  An in-range code on such a row gives -inf - -inf = NaN in both.
+ * One workgroup = one (b, m) x 256 photos, one thread per photo running its token chain; the photos' codes are staged through LDS in
+ * slabs of 32 tokens, the logits gathered from global memory (the photo tiles of a view run on one XCD and share its L2).  No atomics, no
+ * workspace: an element's bits depend on its own (b, m, p) inputs only — not on B, M, P, the grid or where the element sits, nor on
+ * whether accuracy is requested.  All index arithmetic is 64-bit (B*M*L*ld and B*M*P may exceed 2^31).  Footprint: reads L codes of each
+ * of the P (or B*P) photos, B*M*L elements of lse (and of idx with accuracy) and the logits named above; writes B*M*P elements of each
+ * output given.  NULL logits / lse / codes / log_likelihood, accuracy without idx, a negative count, L <= 0, V <= 0, ld < V,
+ * codes_scene_stride < 0 or 0 < codes_scene_stride < P*L: VF_ERR_BAD_ARG; B*M*ceil(P/256) >= 2^31 (the grid): VF_ERR_UNSUPPORTED; both
+ * before any launch.  B*M*P == 0 is a no-op. */
+int vf_match_views_f32(const float* logits, int64_t ld, const float* lse, const int64_t* idx, const int32_t* codes, int64_t codes_scene_stride,
+                       int64_t B, int64_t M, int64_t P, int L, int V, float* log_likelihood, float* accuracy, void* stream);
 /* S reproducible draws per row of fp32 logits [rows][ld >= N] under temperature, top-k and top-p (csrc/sample_rows.hip): one wave per row,
  * the row read once into registers for N <= 1024.  Per row z, sample s < S and row_id (row_id[r], or r where row_id is NULL):
  *   y_n = z_n / temperature; a -inf logit has probability 0 and is never kept;

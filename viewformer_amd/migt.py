@@ -540,6 +540,47 @@ class MIGT:
         return dict(token_log_prob=tlp.view(B, N, *tshape), log_likelihood=ll.view(B, N), predicted_codes=st['idx'].view(B, N, *tshape),
                     confidence=conf.view(B, N, *tshape), entropy=st['entropy'].view(B, N, *tshape), accuracy=acc.view(B, N))
 
+    def match_from_context(self, cache, query_cameras, codes, n_context=None):
+        """Which of M cameras does each of P photos belong to?  ``query_cameras`` fp32 [B,M,7] in the context's (relative, normalised)
+        frame, ``codes`` int [B,P,t,t] or [1,P,t,t] (one photo set for all scenes) -> dict of
+            log_likelihood  fp32 [B,P,M]     of photo p under the MASK view at camera m: what ``score_from_context(cache,
+                                             query_cameras[:, m:m+1], codes[:, p:p+1])['log_likelihood'][:, 0]`` gives, bit for bit
+            accuracy        fp32 [B,P,M]     share of photo p's tokens that view m predicts, likewise
+            predicted_codes int64 [B,M,t,t], confidence fp32 [B,M,t,t], entropy fp32 [B,M,t,t]: of the cameras, as ``score_from_context``'s
+        A scored view's logits depend on the context and the camera only, so the P x M matrix costs M query views (``_query_rows``, as
+        ``score_from_context``: the cache's form stays the cache's business), one LM head over them with the logits written, the row
+        kernel, and one gather-and-sum launch (``ops.match_views``) — never the fused head, which writes no logits.  ``log_likelihood``
+        and ``accuracy`` are TRANSPOSED VIEWS of the kernel's camera-major [B,M,P] output (not contiguous); a code outside
+        [0, n_embeddings) makes its photo's log-likelihood -inf.  M = 0: empty tensors, nothing is launched; P = 0: an empty matrix
+        beside the cameras' own outputs, without the matching launch.  ``n_context``: as ``score_from_context``'s (an int, [B] or [B,M])."""
+        what = 'match_from_context'
+        query_cameras, _, M, L, _ = self._context_args(what, cache, query_cameras, lengths=False)
+        dev, nE, B, tshape = self.device, self.config.n_embeddings, cache.B, cache.tshape
+        codes = torch.as_tensor(codes).to(dev)
+        if (codes.dim() != 2 + len(tshape) or codes.shape[0] not in (1, B) or tuple(codes.shape[2:]) != tshape or codes.dtype.is_floating_point
+                or codes.dtype == torch.bool):
+            raise ValueError(f'{what}: codes int [B={B} or 1,P,{",".join(map(str, tshape))}] expected for this cache, got {codes.dtype} '
+                             f'{tuple(codes.shape)}')
+        ctx = self._context_lengths(cache, n_context, M)
+        P = codes.shape[1]
+        R = B * M * L
+        empty = lambda: torch.empty((B, M, P), dtype=torch.float32, device=dev).transpose(1, 2)
+        if M == 0:                                                           # nothing is launched
+            e4 = lambda dt: torch.empty((B, 0, *tshape), dtype=dt, device=dev)
+            return dict(log_likelihood=empty(), accuracy=empty(), predicted_codes=e4(torch.int64), confidence=e4(torch.float32),
+                        entropy=e4(torch.float32))
+        hf = self._query_rows(cache, *self._mask_rows(query_cameras, L), M, ctx)
+        lg = torch.empty((R, nE), dtype=torch.float32, device=dev)
+        self._lm(hf, R, lg)                                                  # migt.py:417
+        st = ops.logits_score(lg, R, nE, want=('idx', 'max_logit', 'lse', 'entropy'))
+        if P == 0:                                                           # the cameras' own outputs; no photo, no matching launch
+            ll, acc = empty(), empty()
+        else:
+            ll, acc = (x.transpose(1, 2) for x in ops.match_views(lg, st['lse'], st['idx'], codes.to(torch.int32).reshape(-1, P, L).contiguous(),
+                                                                  B, M, P, L, nE))
+        return dict(log_likelihood=ll, accuracy=acc, predicted_codes=st['idx'].view(B, M, *tshape),
+                    confidence=(st['max_logit'] - st['lse']).view(B, M, *tshape), entropy=st['entropy'].view(B, M, *tshape))
+
     # ------------------------------------------------------------------ gradient of the score with respect to the query cameras
     def _dense_T(self, name):
         """the native-fp32 TRANSPOSED pack of a dense layer, for dx = dy @ W^T on ``ops.igemm`` (MIGTTrainer._linear_dx's last branch), made

@@ -934,6 +934,37 @@ def score_views(stats, target, views, L):
     return tlp, conf, ll, acc
 
 
+def match_views(logits, lse, idx, codes, B, M, P, L, V, ld=None, want_accuracy=True):
+    """P photos against M cameras per scene from the M scored views (vf_match_views_f32; include/vf_hip.h has the definition): ``logits``
+    fp32 [B*M*L][ld >= V], ``lse`` fp32 and ``idx`` int64 [B*M*L] as ``logits_score`` gives them (``idx`` may be None without
+    ``want_accuracy``), ``codes`` int32 [B or 1, P, L] (a leading 1: one photo set shared by all scenes).  Returns (log_likelihood,
+    accuracy or None), fp32 [B, M, P] each: camera-major, the sum of a photo's token log-probabilities as one fp32 chain in token order
+    and the share of its tokens the view predicts."""
+    _f32(logits, 'logits')
+    _f32(lse, 'lse')
+    _chk(codes, torch.int32, 'codes')
+    ld = V if ld is None else ld
+    if want_accuracy and idx is None:
+        raise ValueError('match_views: accuracy needs idx')
+    if idx is not None:
+        _chk(idx, torch.int64, 'idx')
+    if codes.dim() != 3 or codes.shape[0] not in (1, B) or tuple(codes.shape[1:]) != (P, L):
+        raise ValueError(f'codes: int32 [{B} or 1, {P}, {L}] expected, got {tuple(codes.shape)}')
+    # the scene stride is the leading dimension's; a photo's L codes and a scene's P photos lie densely
+    stride = codes.stride(0) if codes.shape[0] > 1 else 0
+    if P and (codes.stride(2) != 1 or (P > 1 and codes.stride(1) != L) or (stride and stride < P * L)):
+        raise ValueError(f'codes: dense photos [{P}, {L}] per scene and a scene stride >= {P * L} expected, got strides {codes.stride()}')
+    if (lse.numel() != B * M * L or not lse.is_contiguous() or (idx is not None and (idx.numel() != B * M * L or not idx.is_contiguous()))
+            or ld < V):
+        raise ValueError(f'match_views: contiguous lse and idx [{B * M * L}] and ld >= {V} expected, got {tuple(lse.shape)}, '
+                         f'{None if idx is None else tuple(idx.shape)}, ld {ld}')
+    ll = torch.empty((B, M, P), dtype=torch.float32, device=logits.device)
+    acc = torch.empty((B, M, P), dtype=torch.float32, device=logits.device) if want_accuracy else None
+    check(_lib.load().vf_match_views_f32(_p(logits), ld, _p(lse), _p(idx) if want_accuracy else None, _p(codes), stride, B, M, P, L, V, _p(ll),
+                                         _p(acc), _stream()), 'vf_match_views_f32')
+    return ll, acc
+
+
 SAMPLE_OUTPUTS = ('idx', 'logp', 'kept', 'thr')
 
 

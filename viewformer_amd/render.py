@@ -656,27 +656,66 @@ class ViewRenderer:
             parts = [tm.score_from_context(self.cache, poses, codes[:, :0], **kw)]      # N = 0: empty tensors of the right shapes
         return {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
 
-    def _photo_codes(self, what, images, codes, N):
-        """``images`` uint8 [B,N or 1,H,W,3] or ``codes`` int [B,N or 1,t,t] (exactly one) -> int32 codes [B,P,t,t], P in (1, N); N None: any P"""
+    def _photo_codes(self, what, images, codes, N, shared: bool = False):
+        """``images`` uint8 [B,N or 1,H,W,3] or ``codes`` int [B,N or 1,t,t] (exactly one) -> int32 codes [B,P,t,t], P in (1, N); N None: any P.
+        ``shared``: the scene axis may also be 1 (one photo set for all scenes) -> [B or 1,P,t,t]"""
         if (images is None) == (codes is None):
             raise ValueError(f'{what}: exactly one of images / codes expected')
         tm, cm = self.transformer, self.codebook
         dev, B, t = cm.device, self.cache.B, tm.config.token_image_size
         views = f'N={N} or 1' if N is not None else 'N'
+        scenes = (1, B) if shared else (B,)
+        Bs = f'B={B} or 1' if shared else f'B={B}'
         if codes is None:
             images = torch.as_tensor(images).to(dev)
-            if images.dim() != 5 or images.shape[0] != B or (N is not None and images.shape[1] not in (1, N)):
-                raise ValueError(f'{what}: images [B={B},{views},H,W,3] expected, got {tuple(images.shape)}')
-            P = images.shape[1]
+            if images.dim() != 5 or images.shape[0] not in scenes or (N is not None and images.shape[1] not in (1, N)):
+                raise ValueError(f'{what}: images [{Bs},{views},H,W,3] expected, got {tuple(images.shape)}')
+            S, P = images.shape[:2]
             codes = (cm.encode(_frames_for_encode(images, cm.config.image_size))[-1] if P
-                     else torch.empty((B, 0, t, t), dtype=torch.int32, device=dev))
+                     else torch.empty((S, 0, t, t), dtype=torch.int32, device=dev))
         else:
             codes = torch.as_tensor(codes).to(dev)
-            if (codes.dim() != 4 or codes.shape[0] != B or (N is not None and codes.shape[1] not in (1, N)) or tuple(codes.shape[2:]) != (t, t)
-                    or codes.dtype.is_floating_point or codes.dtype == torch.bool):
-                raise ValueError(f'{what}: codes int [B={B},{views},{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
-            P = codes.shape[1]
-        return codes.to(torch.int32).view(B, P, t, t)
+            if (codes.dim() != 4 or codes.shape[0] not in scenes or (N is not None and codes.shape[1] not in (1, N))
+                    or tuple(codes.shape[2:]) != (t, t) or codes.dtype.is_floating_point or codes.dtype == torch.bool):
+                raise ValueError(f'{what}: codes int [{Bs},{views},{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
+            S, P = codes.shape[:2]
+        return codes.to(torch.int32).view(S, P, t, t)
+
+    def match(self, query_cameras, images=None, codes=None, max_views_per_call: int = None, n_context=None):
+        """Which of M cameras does each of P photos belong to, and which photo does each camera expect?  ``query_cameras`` [B,M,7] in the
+        caller's world frame (the context's) and ``images`` uint8 [B or 1,P,H,W,3] (host or device; resized for the encoder as the
+        evaluators do, each photo encoded once) or ``codes`` int [B or 1,P,t,t] (already encoded; a scene axis of 1: one photo set for
+        all scenes, e.g. ``bank.codes[None]``) -> ``MIGT.match_from_context``'s dict — log_likelihood, accuracy fp32 [B,P,M] (element
+        [b,p,m] is ``score``'s for photo p at camera m, bit for bit; possibly a transposed view); predicted_codes, confidence, entropy
+        [B,M,t,t] — plus
+            best_camera  int64 [B,P]   the camera under which each photo is most likely
+            best_photo   int64 [B,M]   the photo each camera's view makes most likely
+        both the FIRST arg-max of log_likelihood (``ops.argmax_rows``: ties to the lowest index; -1 where there is nothing to choose
+        from, M = 0 or P = 0).  The transformer runs M query views, not P x M.  M is walked in chunks of whole views
+        (``plan_view_chunks``); an element does not depend on the chunking; P is not chunked.  ``n_context``: as ``render``'s, per camera."""
+        self._context('match')
+        query_cameras = self._world_cameras('match', query_cameras)
+        B, M = self.cache.B, query_cameras.shape[1]
+        codes = self._photo_codes('match', images, codes, None, shared=True)
+        P = codes.shape[1]
+        dev = query_cameras.device
+        poses = query_poses(query_cameras, self.transform)
+        lens = self._lengths(n_context, M)
+        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
+        tm = self.transformer
+        parts = [tm.match_from_context(self.cache, poses[:, a:b], codes, **lkw(a, b)) for a, b in plan_view_chunks(M, B, max_views_per_call)]
+        if not parts:
+            parts = [tm.match_from_context(self.cache, poses, codes)]                   # M = 0: empty tensors of the right shapes
+        cat = lambda k: torch.cat([p[k] for p in parts], 2 if k in ('log_likelihood', 'accuracy') else 1) if len(parts) > 1 else parts[0][k]
+        res = {k: cat(k) for k in parts[0]}
+        ll = res['log_likelihood']
+        none = lambda n: torch.full((B, n), -1, dtype=torch.int64, device=dev)
+        if M and P:
+            res['best_camera'] = ops.argmax_rows(ll.contiguous().view(B * P, M), B * P, M).view(B, P)
+            res['best_photo'] = ops.argmax_rows(ll.transpose(1, 2).contiguous().view(B * M, P), B * M, P).view(B, M)
+        else:
+            res['best_camera'], res['best_photo'] = none(P), none(M)
+        return res
 
     def _world_cameras(self, what, cameras):
         cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.codebook.device)
@@ -882,6 +921,15 @@ def score_views(transformer_model, codebook_model, images, cameras, query_camera
     (the photos' codes instead of ``photos``), ``max_views_per_call``."""
     r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
     return r.score(query_cameras, images=photos, codes=kw.pop('photo_codes', None), **kw)
+
+
+def match_views(transformer_model, codebook_model, images, cameras, query_cameras, photos=None, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7], ``query_cameras`` [B,M,7] and ``photos`` uint8
+    [B or 1,P,H,W,3] -> ``ViewRenderer.match``'s dict (the [B,P,M] likelihoods from M query views, best_camera, best_photo).  Keywords:
+    ``codes`` (context codes instead of images; pass images=None), ``photo_codes`` (the photos' codes instead of ``photos``),
+    ``max_views_per_call``, ``n_context``."""
+    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    return r.match(query_cameras, images=photos, codes=kw.pop('photo_codes', None), **kw)
 
 
 def refine_views(transformer_model, codebook_model, images, cameras, photos=None, cameras0=None, **kw):
