@@ -181,35 +181,7 @@ def test_ops_match_views_refuses_on_the_host(lib):
 
 
 # ------------------------------------------------------------------ host side of ViewRenderer.match
-class _Cfg:
-    token_image_size = 8
-    n_embeddings = 128
-    augment_poses = 'relative'
-    image_size = 32
-
-
-class _FakeCache:
-    B = 2
-
-
-class _FakeModel:
-    config = _Cfg()
-
-    def __init__(self):
-        self.calls = []
-
-    def match_from_context(self, cache, poses, codes, **kw):
-        self.calls.append((tuple(poses.shape), tuple(codes.shape), kw))
-        B, M = poses.shape[:2]
-        P = codes.shape[1]
-        e = lambda dt: torch.zeros((B, M, 8, 8), dtype=dt)
-        m = torch.zeros((B, M, P)).transpose(1, 2)
-        return dict(log_likelihood=m, accuracy=m.clone(), predicted_codes=e(torch.int64), confidence=e(torch.float32), entropy=e(torch.float32))
-
-
-class _FakeCodebook:
-    device = torch.device('cpu')
-    config = _Cfg()
+from render_fakes import Cfg as _Cfg, FakeCache as _FakeCache, FakeCodebook as _FakeCodebook, FakeModel as _FakeModel  # noqa: F401
 
 
 def _renderer():

@@ -335,37 +335,7 @@ def test_ops_refuse_cpu_tensors_and_unknown_outputs(lib):
 
 
 # ------------------------------------------------------------------ host plumbing of ViewRenderer.sample
-class _Cfg:
-    token_image_size = 8
-    n_embeddings = 128
-    augment_poses = 'relative'
-    image_size = 32
-
-
-class _FakeCache:
-    B = 2
-
-
-class _FakeModel:
-    """records what ViewRenderer.sample hands to sample_from_context; a token's 'draw' is a function of its pose, view number and sample"""
-    config = _Cfg()
-
-    def __init__(self):
-        self.calls = []
-
-    def sample_from_context(self, cache, poses, n_samples=1, view0=0, **kw):
-        self.calls.append((tuple(poses.shape), n_samples, view0, kw))
-        B, N = poses.shape[:2]
-        S = n_samples
-        view = (torch.arange(N) + view0).view(1, N, 1, 1, 1) * 10 + torch.arange(S).view(1, 1, S, 1, 1)
-        codes = (view + torch.zeros((B, N, S, 8, 8), dtype=torch.int64))
-        tok = codes.float() + poses[..., 0].view(B, N, 1, 1, 1)
-        return dict(codes=codes, token_log_prob=tok, log_likelihood=tok.sum((3, 4)), kept=torch.ones((B, N, 8, 8), dtype=torch.int32))
-
-
-class _FakeCodebook:
-    device = torch.device('cpu')
-    config = _Cfg()
+from render_fakes import Cfg as _Cfg, FakeCache as _FakeCache, FakeCodebook as _FakeCodebook, FakeModel as _FakeModel  # noqa: F401
 
 
 def _renderer():

@@ -214,42 +214,7 @@ def test_ops_refuse_cpu_tensors_and_unknown_outputs(lib):
 
 
 # ------------------------------------------------------------------ host plumbing of ViewRenderer.score
-class _Cfg:
-    token_image_size = 8
-    n_embeddings = 128
-    augment_poses = 'relative'
-    image_size = 32
-
-
-class _FakeCache:
-    B = 2
-
-
-class _FakeModel:
-    """records what ViewRenderer.score hands to score_from_context; the 'score' of a view is a function of its pose and codes"""
-    config = _Cfg()
-
-    def __init__(self):
-        self.calls = []
-
-    def score_from_context(self, cache, poses, codes, **kw):
-        self.calls.append((tuple(poses.shape), tuple(codes.shape), kw))
-        B, N = poses.shape[:2]
-        c = codes.expand(B, N, 8, 8).float()
-        tok = c + poses[..., 0].view(B, N, 1, 1)
-        return dict(token_log_prob=tok, log_likelihood=tok.sum((2, 3)), predicted_codes=c.long(), confidence=tok, entropy=tok, accuracy=tok.mean((2, 3)))
-
-
-class _FakeCodebook:
-    device = torch.device('cpu')
-    config = _Cfg()
-
-    def __init__(self):
-        self.encoded = 0
-
-    def encode(self, frames):
-        self.encoded += frames.shape[0]
-        return (None, frames.reshape(frames.shape[0], -1)[:, :64].to(torch.int32).view(-1, 8, 8))
+from render_fakes import Cfg as _Cfg, FakeCache as _FakeCache, FakeCodebook as _FakeCodebook, FakeModel as _FakeModel  # noqa: F401
 
 
 def _renderer(transform=True):

@@ -126,6 +126,15 @@ def plan_view_chunks(n_views: int, n_scenes: int = 1, max_views_per_call: int = 
     return [(a, min(a + cap, n_views)) for a in range(0, n_views, cap)]
 
 
+def _int_array(what, x, ndim=(1,), low: int = 0):
+    """``x`` — host data or a tensor (a device tensor is brought to the host once) — as a numpy array of integers, not bool, with one
+    of ``ndim`` dimensions and no value below ``low``; anything else: ValueError naming ``what``.  Pure."""
+    a = np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x)
+    if a.ndim not in ndim or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or (a.size and a.min() < low):
+        raise ValueError(f'{what}: integers >= {low} with {" or ".join(map(str, ndim))} dimension(s) expected, got {x}')
+    return a
+
+
 def plan_context_lengths(n_context, B: int, N: int, C: int, scene_default=None):
     """Context lengths of N query views per scene, normalised: ``n_context`` — an int, [B] (one length per scene) or [B,N] (one per
     query view) of integers in [0, C]; host data preferred, a device tensor is brought to the host once — -> int32 array [B,N].
@@ -194,9 +203,9 @@ def plan_rollout_lengths(lengths, T: int):
     ``gen[t, b] = lengths[b] + t``: what the MASK view of step t sees (the context and the generated views 0 ... t-1), and also the
     cache view that the generated view t is appended at, seeing as many.  ``pair[t, b]`` = (gen[t-1, b], gen[t, b]): the fused step's
     two views per scene, the append view of step t-1 and the MASK view of step t (row 0, which has no append view, is not used).  Pure."""
-    a = np.asarray(lengths)
-    if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or T < 0 or (a.size and a.min() < 0):
-        raise ValueError(f'plan_rollout_lengths: lengths, [B] integers >= 0, and T >= 0 expected, got {lengths} and {T}')
+    a = _int_array('plan_rollout_lengths: lengths [B]', lengths)
+    if T < 0:
+        raise ValueError(f'plan_rollout_lengths: T >= 0 expected, got {T}')
     gen = (a.astype(np.int64).reshape(1, -1) + np.arange(T, dtype=np.int64).reshape(T, 1)).astype(np.int32)
     pair = np.stack([gen - 1, gen], -1)
     return np.ascontiguousarray(gen), np.ascontiguousarray(pair)
@@ -212,9 +221,9 @@ def plan_replication(B: int, S: int):
 def plan_fork(lengths, S: int):
     """The children of a fork of scenes with ``lengths`` [B] filled views, S per scene: (split int32 [B*S], parent int64 [B*S]).  Child
     scene b*S+s (the order of ``plan_replication``) starts at ``split = lengths[b]`` logical views, all of them parent scene b's.  Pure."""
-    a = np.asarray(lengths)
-    if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or S < 1 or (a.size and a.min() < 0):
-        raise ValueError(f'plan_fork: lengths, [B] integers >= 0, and S >= 1 expected, got {lengths} and {S}')
+    a = _int_array('plan_fork: lengths [B]', lengths)
+    if S < 1:
+        raise ValueError(f'plan_fork: S >= 1 expected, got {S}')
     parent = plan_replication(a.shape[0], S)
     return np.ascontiguousarray(a[parent].astype(np.int32)), parent
 
@@ -223,9 +232,9 @@ def map_fork_views(split, n_views: int):
     """Where the logical views 0 ... n_views-1 of every scene of a fork lie: (segment int8 [B,n_views], view int32 [B,n_views]) —
     segment 0 = the parent's buffers, view s, for s < split[b]; segment 1 = the scene's own buffers, view s - split[b], otherwise.  This
     is the mapping of ``vf_attn_prefix_fork_*`` and of the own-buffer appends.  Pure."""
-    a = np.asarray(split)
-    if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or n_views < 0 or (a.size and a.min() < 0):
-        raise ValueError(f'map_fork_views: split, [B] integers >= 0, and n_views >= 0 expected, got {split} and {n_views}')
+    a = _int_array('map_fork_views: split [B]', split)
+    if n_views < 0:
+        raise ValueError(f'map_fork_views: n_views >= 0 expected, got {n_views}')
     s = np.arange(n_views, dtype=np.int64).reshape(1, n_views)
     sp = a.astype(np.int64).reshape(-1, 1)
     own = s >= sp
@@ -235,10 +244,8 @@ def map_fork_views(split, n_views: int):
 def plan_fork_lengths(split, lengths, room: int):
     """The own views of a fork's scenes: ``lengths - split`` int32 [B], validated — logical ``lengths`` [B] of at least ``split`` and at
     most ``split + room``, and the same number of own views in every scene (children grow together).  Pure."""
-    sp, ln = np.asarray(split), np.asarray(lengths)
-    ok = (sp.ndim == 1 and sp.shape == ln.shape and np.issubdtype(sp.dtype, np.integer) and np.issubdtype(ln.dtype, np.integer)
-          and sp.dtype != np.bool_ and ln.dtype != np.bool_ and room >= 0)
-    if not ok or (sp.size and (sp.min() < 0 or (ln < sp).any() or (ln > sp.astype(np.int64) + room).any())):
+    sp, ln = _int_array('plan_fork_lengths: split [B]', split), _int_array('plan_fork_lengths: lengths [B]', lengths)
+    if sp.shape != ln.shape or room < 0 or (ln < sp).any() or (ln > sp.astype(np.int64) + room).any():
         raise ValueError(f'plan_fork_lengths: split <= lengths <= split + room = {room}, [B] integers, expected, got {split} and {lengths}')
     own = (ln.astype(np.int64) - sp).astype(np.int32)
     if own.size and (own != own[0]).any():
@@ -286,37 +293,20 @@ class ViewRenderer:
         ``pack``: None, ``'kv'`` or ``'e4m3'`` (bf16 models): the context is filled as a GROWING packed cache of that form directly
         (``MIGT.prefill_context(pack=...)``: the plain cache never exists), as ``set_context(...)`` then ``pack(dtype, room=capacity - C)``
         would leave it, bit for bit."""
-        tm, cm = self.transformer, self.codebook
-        dev = cm.device
-        if cameras is None or (images is None) == (codes is None):
-            raise ValueError('set_context: cameras and exactly one of images / codes expected')
-        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(dev)
-        if cameras.dim() != 3 or cameras.shape[-1] != 7 or cameras.shape[1] < 1:
-            raise ValueError(f'set_context: cameras [B,C,7] expected, got {tuple(cameras.shape)}')
+        if cameras is None:
+            raise ValueError('set_context: cameras expected')
+        cameras = self._world_cameras('set_context', cameras, new=True)
         B, C = cameras.shape[:2]
-        t = tm.config.token_image_size
-        if n_context is not None:
-            a = np.asarray(n_context.detach().cpu().numpy() if isinstance(n_context, torch.Tensor) else n_context)
-            if a.ndim > 1 or (a.ndim == 1 and a.shape != (B,)):
-                raise ValueError(f'set_context: n_context an int or [B={B}] expected, got {a.shape}')
-            n_context = plan_context_lengths(a, B, 1, C)[:, 0].copy()
-            if n_context.size and n_context.min() < 1:
-                raise ValueError(f'set_context: n_context in [1, C={C}] expected (a scene has at least one context view), got {int(n_context.min())}')
-        poses, transform = context_poses(cameras, tm.config.augment_poses)
-        if codes is None:
-            images = torch.as_tensor(images).to(dev)
-            if images.dim() != 5 or tuple(images.shape[:2]) != (B, C):
-                raise ValueError(f'set_context: images [B,C,H,W,3] with one frame per camera of {tuple(cameras.shape)} expected, got {tuple(images.shape)}')
-            codes = cm.encode(_frames_for_encode(images, cm.config.image_size))[-1]
-        else:
-            codes = torch.as_tensor(codes).to(dev)
-            if codes.numel() != B * C * t * t:
-                raise ValueError(f'set_context: codes {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
-        codes = codes.to(torch.int32).view(B, C, t, t)
+        if C < 1:
+            raise ValueError(f'set_context: at least one context view expected, got cameras {tuple(cameras.shape)}')
+        if n_context is not None:                                        # an int or [B], in [1, C]: a scene has at least one context view
+            n_context = plan_context_lengths(_int_array('set_context: n_context', n_context, ndim=(0, 1), low=1), B, 1, C)[:, 0].copy()
+        codes = self._photo_codes('set_context', images, codes, B, (C,))
+        poses, transform = context_poses(cameras, self.transformer.config.augment_poses)
         kw = {} if pack is None else dict(pack=pack)
         if capacity is not None:
             kw['capacity'] = capacity
-        self.cache = tm.prefill_context(codes, poses, **kw)
+        self.cache = self.transformer.prefill_context(codes, poses, **kw)
         self.transform, self.context_codes, self.n_context = transform, codes, n_context
         return self
 
@@ -383,30 +373,13 @@ class ViewRenderer:
         ``sample``, ``score``, ``localize`` and ``sweep`` sees the grown context; ``n_context`` and ``context_codes`` follow."""
         self._context('append')
         self._refuse_growth('append')
-        if cameras is None or (images is None) == (codes is None):
-            raise ValueError('append: cameras and exactly one of images / codes expected')
-        tm, cm = self.transformer, self.codebook
-        dev = cm.device
-        B = self.cache.B
-        t = tm.config.token_image_size
-        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(dev)
-        if cameras.dim() != 3 or cameras.shape[0] != B or cameras.shape[-1] != 7:
-            raise ValueError(f'append: cameras [B={B},K,7] expected, got {tuple(cameras.shape)}')
-        K = cameras.shape[1]
-        if codes is None:
-            images = torch.as_tensor(images).to(dev)
-            if images.dim() != 5 or tuple(images.shape[:2]) != (B, K):
-                raise ValueError(f'append: images [B,K,H,W,3] with one frame per camera of {tuple(cameras.shape)} expected, got {tuple(images.shape)}')
-            codes = (cm.encode(_frames_for_encode(images, cm.config.image_size))[-1] if K
-                     else torch.empty((B, 0, t, t), dtype=torch.int32, device=dev))
-        else:
-            codes = torch.as_tensor(codes).to(dev)
-            if codes.numel() != B * K * t * t or codes.dtype.is_floating_point:
-                raise ValueError(f'append: codes int {tuple(codes.shape)}: one [t,t] map per camera of {tuple(cameras.shape)} expected')
-        codes = codes.to(torch.int32).view(B, K, t, t)
+        if cameras is None:
+            raise ValueError('append: cameras expected')
+        cameras = self._world_cameras('append', cameras)
+        codes = self._photo_codes('append', images, codes, self.cache.B, (cameras.shape[1],))
         self._own_lengths(self.cache)
         before = self.cache.filled()
-        tm.append_to_context(self.cache, codes, query_poses(cameras, self.transform))
+        self.transformer.append_to_context(self.cache, codes, query_poses(cameras, self.transform))
         self._add_codes(before, codes)
         return self
 
@@ -455,12 +428,8 @@ class ViewRenderer:
             raise ValueError('rollout: adopt goes with fork=True and n_samples > 1 (keep=True keeps the one trajectory of n_samples = 1)')
         if adopt is not None and isinstance(adopt, str) and adopt != 'best':
             raise ValueError(f"rollout: adopt 'best' or an int [B] expected, got {adopt!r}")
-        tm, cm = self.transformer, self.codebook
-        dev = cm.device
-        B = self.cache.B
-        path_cameras = torch.as_tensor(path_cameras, dtype=torch.float32).to(dev)
-        if path_cameras.dim() != 3 or path_cameras.shape[0] != B or path_cameras.shape[-1] != 7:
-            raise ValueError(f'rollout: path_cameras [B={B},T,7] expected, got {tuple(path_cameras.shape)}')
+        tm, B = self.transformer, self.cache.B
+        path_cameras = self._world_cameras('rollout', path_cameras)
         S = int(n_samples)
         if S < 1 or S != n_samples:
             raise ValueError(f'rollout: n_samples >= 1 expected, got {n_samples}')
@@ -520,12 +489,6 @@ class ViewRenderer:
         dec = torch.cat(decs) if len(decs) > 1 else (decs[0] if decs else torch.empty((0, *img.shape[1:]), dtype=torch.float32, device=dev))
         return img, dec
 
-    def _lengths(self, n_context, N):
-        """the methods' ``n_context`` (an int, [B] or [B,N]; None: ``set_context``'s per-scene default) -> int32 [B,N] or None"""
-        if n_context is None and self.n_context is None:
-            return None                                                  # the rectangular path: nothing is asked of the cache
-        return plan_context_lengths(n_context, self.cache.B, N, self.cache.C, scene_default=self.n_context)
-
     def render(self, query_cameras, max_views_per_call: int = None, return_codes: bool = False, return_confidence: bool = False,
                n_context=None):
         """``query_cameras`` [B,N,7] in the caller's world frame (the context's) -> dict(generated_images uint8 [B,N,H,W,3]); with
@@ -537,20 +500,14 @@ class ViewRenderer:
         ``set_context``'s per-scene default; sliced per chunk with the views.  4 (bf16) / 2 (f32) consecutive views share an attention
         workgroup, which costs what its longest member costs: keep equal lengths together (``sweep`` does)."""
         self._context('render')
-        tm, cm = self.transformer, self.codebook
-        dev = cm.device
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
-        B = self.cache.B
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
-            raise ValueError(f'render: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
-        N = query_cameras.shape[1]
+        query_cameras = self._world_cameras('render', query_cameras)
+        tm, dev = self.transformer, query_cameras.device
+        B, N = self.cache.B, query_cameras.shape[1]
         t = tm.config.token_image_size
         nE = tm.config.n_embeddings
         poses = query_poses(query_cameras, self.transform)
-        lens = self._lengths(n_context, N)
         gen, lgs, conf, ent = [], [], [], []
-        for a, b in plan_view_chunks(N, B, max_views_per_call):
-            kw = {} if lens is None else dict(n_context=lens[:, a:b])
+        for a, b, kw in self._chunks(N, max_views_per_call, n_context):   # (no call at N = 0, unlike ``_walk``: the empties are made here)
             if return_confidence and not return_codes:
                 g, cf, en = tm.generate_from_context(self.cache, poses[:, a:b], codes_only=True, return_confidence=True, **kw)
                 gen.append(g); conf.append(cf); ent.append(en)
@@ -588,24 +545,14 @@ class ViewRenderer:
         seed (same distribution, same kept sets, same ``top_k = 1`` result); only scene 0 of a batch reproduces its stand-alone draws.
         ``n_context``: as ``render``'s."""
         self._context('sample')
-        tm, cm = self.transformer, self.codebook
-        dev = cm.device
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
-        B = self.cache.B
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
-            raise ValueError(f'sample: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
-        N = query_cameras.shape[1]
-        S = int(n_samples)
+        query_cameras = self._world_cameras('sample', query_cameras)
+        tm = self.transformer
+        B, N, S = self.cache.B, query_cameras.shape[1], int(n_samples)
         t = tm.config.token_image_size
         poses = query_poses(query_cameras, self.transform)
         kw = dict(n_samples=S, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
-        lens = self._lengths(n_context, N)
-        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
-        parts = [tm.sample_from_context(self.cache, poses[:, a:b], view0=a, **kw, **lkw(a, b))
-                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
-        if not parts:
-            parts = [tm.sample_from_context(self.cache, poses, **kw)]               # N = 0: empty tensors of the right shapes
-        out = {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        out = self._walk(N, max_views_per_call, n_context,               # every chunk is told its first view's number (the empty range is not)
+                         lambda a, b, **lkw: tm.sample_from_context(self.cache, poses[:, a:b], **(dict(view0=a) if b else {}), **kw, **lkw))
         img, _ = self._decode(out['codes'].reshape(B * N * S, t, t))
         res = dict(generated_images=img.view(B, N, S, *img.shape[1:]), log_likelihood=out['log_likelihood'])
         if return_codes:
@@ -621,65 +568,75 @@ class ViewRenderer:
         chunking.  ``self.fused_score`` (None = the model's default route, True / False = the fused head / through the logits) is for A/B runs.
         ``n_context``: as ``render``'s."""
         self._context('score')
-        if (images is None) == (codes is None):
-            raise ValueError('score: exactly one of images / codes expected')
-        tm, cm = self.transformer, self.codebook
-        dev = cm.device
-        B = self.cache.B
-        t = tm.config.token_image_size
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(dev)
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
-            raise ValueError(f'score: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
+        query_cameras = self._world_cameras('score', query_cameras)
         N = query_cameras.shape[1]
-        if codes is None:
-            images = torch.as_tensor(images).to(dev)
-            if images.dim() != 5 or images.shape[0] != B or images.shape[1] not in (1, N):
-                raise ValueError(f'score: images [B={B},N={N} or 1,H,W,3] expected, got {tuple(images.shape)}')
-            P = images.shape[1]
-            codes = (cm.encode(_frames_for_encode(images, cm.config.image_size))[-1] if P
-                     else torch.empty((B, 0, t, t), dtype=torch.int32, device=dev))
-        else:
-            codes = torch.as_tensor(codes).to(dev)
-            if (codes.dim() != 4 or codes.shape[0] != B or codes.shape[1] not in (1, N) or tuple(codes.shape[2:]) != (t, t)
-                    or codes.dtype.is_floating_point):
-                raise ValueError(f'score: codes int [B={B},N={N} or 1,{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
-            P = codes.shape[1]
-        codes = codes.to(torch.int32).view(B, P, t, t)
+        photo = self._per_view(self._photo_codes('score', images, codes, self.cache.B, (1, N)), N)
         poses = query_poses(query_cameras, self.transform)
         kw = {} if self.fused_score is None else dict(fused=bool(self.fused_score))
-        one = P == 1 and N != 1
-        lens = self._lengths(n_context, N)
-        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
-        parts = [tm.score_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **kw, **lkw(a, b))
-                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
-        if not parts:
-            parts = [tm.score_from_context(self.cache, poses, codes[:, :0], **kw)]      # N = 0: empty tensors of the right shapes
-        return {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        return self._walk(N, max_views_per_call, n_context,
+                          lambda a, b, **lkw: self.transformer.score_from_context(self.cache, poses[:, a:b], photo(a, b), **kw, **lkw))
 
-    def _photo_codes(self, what, images, codes, N, shared: bool = False):
-        """``images`` uint8 [B,N or 1,H,W,3] or ``codes`` int [B,N or 1,t,t] (exactly one) -> int32 codes [B,P,t,t], P in (1, N); N None: any P.
-        ``shared``: the scene axis may also be 1 (one photo set for all scenes) -> [B or 1,P,t,t]"""
+    # ------------------------------------------------------------------ the front matter, once (DESIGN.md §6.25)
+    def _world_cameras(self, what, cameras, new: bool = False):
+        """``cameras`` [B,N,7] in the caller's world frame (host or device) -> fp32 on the codebook's device; B is the context's, or
+        with ``new`` (``set_context``, which has no context yet) the cameras' own"""
+        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.codebook.device)
+        if cameras.dim() != 3 or cameras.shape[-1] != 7 or not (new or cameras.shape[0] == self.cache.B):
+            raise ValueError(f'{what}: cameras [B{"" if new else "=%d" % self.cache.B},N,7] expected, got {tuple(cameras.shape)}')
+        return cameras
+
+    def _photo_codes(self, what, images, codes, B, views=None, shared: bool = False):
+        """``images`` uint8 [B,P,H,W,3] (host or device; resized for the encoder as the evaluators do, encoded once; P = 0 encodes
+        nothing) or ``codes`` [B,P,t,t] (exactly one of the two) -> int32 codes [B,P,t,t].  ``views``: the values P may take — (K,): one
+        photo per camera, (1, N): one per camera or one per scene, None: any; ``shared``: the scene axis may also be 1 (one photo set for
+        all scenes) -> [1,P,t,t].  Codes are integers (not bool, not floating point) of exactly that shape: nothing is reshaped or
+        truncated on the caller's behalf."""
         if (images is None) == (codes is None):
             raise ValueError(f'{what}: exactly one of images / codes expected')
-        tm, cm = self.transformer, self.codebook
-        dev, B, t = cm.device, self.cache.B, tm.config.token_image_size
-        views = f'N={N} or 1' if N is not None else 'N'
+        cm, t = self.codebook, self.transformer.config.token_image_size
         scenes = (1, B) if shared else (B,)
-        Bs = f'B={B} or 1' if shared else f'B={B}'
+        where = f'[{" or ".join(map(str, scenes))} scenes, {"any number of" if views is None else " or ".join(map(str, views))} views'
         if codes is None:
-            images = torch.as_tensor(images).to(dev)
-            if images.dim() != 5 or images.shape[0] not in scenes or (N is not None and images.shape[1] not in (1, N)):
-                raise ValueError(f'{what}: images [{Bs},{views},H,W,3] expected, got {tuple(images.shape)}')
+            images = torch.as_tensor(images).to(cm.device)
+            if images.dim() != 5 or images.shape[0] not in scenes or (views is not None and images.shape[1] not in views):
+                raise ValueError(f'{what}: images {where},H,W,3] expected, got {tuple(images.shape)}')
             S, P = images.shape[:2]
             codes = (cm.encode(_frames_for_encode(images, cm.config.image_size))[-1] if P
-                     else torch.empty((S, 0, t, t), dtype=torch.int32, device=dev))
+                     else torch.empty((S, 0, t, t), dtype=torch.int32, device=cm.device))
         else:
-            codes = torch.as_tensor(codes).to(dev)
-            if (codes.dim() != 4 or codes.shape[0] not in scenes or (N is not None and codes.shape[1] not in (1, N))
+            codes = torch.as_tensor(codes).to(cm.device)
+            if (codes.dim() != 4 or codes.shape[0] not in scenes or (views is not None and codes.shape[1] not in views)
                     or tuple(codes.shape[2:]) != (t, t) or codes.dtype.is_floating_point or codes.dtype == torch.bool):
-                raise ValueError(f'{what}: codes int [{Bs},{views},{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
+                raise ValueError(f'{what}: codes int {where},{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
             S, P = codes.shape[:2]
         return codes.to(torch.int32).view(S, P, t, t)
+
+    @staticmethod
+    def _per_view(codes, N):
+        """the photos of the views a ... b-1 of N: their own, or the scene's one photo for all of them"""
+        one = codes.shape[1] == 1 and N > 1
+        return lambda a, b: codes if one else codes[:, a:b]
+
+    def _lengths(self, n_context, N):
+        """the methods' ``n_context`` (an int, [B] or [B,N]; None: ``set_context``'s per-scene default) -> int32 [B,N] or None"""
+        if n_context is None and self.n_context is None:
+            return None                                                  # the rectangular path: nothing is asked of the cache
+        return plan_context_lengths(n_context, self.cache.B, N, self.cache.C, scene_default=self.n_context)
+
+    def _chunks(self, N, max_views_per_call, n_context):
+        """[(a, b, keywords)] over the N views of every scene, in whole views (``plan_view_chunks``): the keywords are the chunk's slice
+        of the context lengths as ``n_context=`` where lengths exist (``_lengths``), and nothing where they do not"""
+        lens = self._lengths(n_context, N)
+        return [(a, b, {} if lens is None else dict(n_context=lens[:, a:b])) for a, b in plan_view_chunks(N, self.cache.B, max_views_per_call)]
+
+    def _walk(self, N, max_views_per_call, n_context, call, axis={}):
+        """``call(a, b, **keywords)`` -> a dict, for every chunk of ``_chunks``; N = 0: the one call on the empty range, ``call(0, 0)``
+        without a length keyword, for the empty tensors of the right shapes.  -> the parts concatenated key by key along axis 1 (the
+        view axis; ``axis``: the keys whose view axis is another), a single part as it is"""
+        parts = [call(a, b, **kw) for a, b, kw in self._chunks(N, max_views_per_call, n_context)]
+        if not parts:
+            parts = [call(0, 0)]
+        return dict(parts[0]) if len(parts) == 1 else {k: torch.cat([p[k] for p in parts], axis.get(k, 1)) for k in parts[0]}
 
     def match(self, query_cameras, images=None, codes=None, max_views_per_call: int = None, n_context=None):
         """Which of M cameras does each of P photos belong to, and which photo does each camera expect?  ``query_cameras`` [B,M,7] in the
@@ -696,18 +653,13 @@ class ViewRenderer:
         self._context('match')
         query_cameras = self._world_cameras('match', query_cameras)
         B, M = self.cache.B, query_cameras.shape[1]
-        codes = self._photo_codes('match', images, codes, None, shared=True)
+        codes = self._photo_codes('match', images, codes, B, shared=True)
         P = codes.shape[1]
         dev = query_cameras.device
         poses = query_poses(query_cameras, self.transform)
-        lens = self._lengths(n_context, M)
-        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
-        tm = self.transformer
-        parts = [tm.match_from_context(self.cache, poses[:, a:b], codes, **lkw(a, b)) for a, b in plan_view_chunks(M, B, max_views_per_call)]
-        if not parts:
-            parts = [tm.match_from_context(self.cache, poses, codes)]                   # M = 0: empty tensors of the right shapes
-        cat = lambda k: torch.cat([p[k] for p in parts], 2 if k in ('log_likelihood', 'accuracy') else 1) if len(parts) > 1 else parts[0][k]
-        res = {k: cat(k) for k in parts[0]}
+        res = self._walk(M, max_views_per_call, n_context,               # P is not chunked; the cameras are the last axis of [B,P,M]
+                         lambda a, b, **lkw: self.transformer.match_from_context(self.cache, poses[:, a:b], codes, **lkw),
+                         axis=dict(log_likelihood=2, accuracy=2))
         ll = res['log_likelihood']
         none = lambda n: torch.full((B, n), -1, dtype=torch.int64, device=dev)
         if M and P:
@@ -716,12 +668,6 @@ class ViewRenderer:
         else:
             res['best_camera'], res['best_photo'] = none(P), none(M)
         return res
-
-    def _world_cameras(self, what, cameras):
-        cameras = torch.as_tensor(cameras, dtype=torch.float32).to(self.codebook.device)
-        if cameras.dim() != 3 or cameras.shape[0] != self.cache.B or cameras.shape[-1] != 7:
-            raise ValueError(f'{what}: cameras [B={self.cache.B},N,7] expected, got {tuple(cameras.shape)}')
-        return cameras
 
     def score_gradient(self, query_cameras, images=None, codes=None, max_views_per_call: int = None, n_context=None):
         """``score`` plus which way each camera should move: ``MIGT.score_grad_from_context``'s dict (``score``'s keys with the same
@@ -732,18 +678,11 @@ class ViewRenderer:
         self._context('score_gradient')
         self.cache.refuse_backward('ViewRenderer.score_gradient')
         query_cameras = self._world_cameras('score_gradient', query_cameras)
-        B, N = self.cache.B, query_cameras.shape[1]
-        codes = self._photo_codes('score_gradient', images, codes, N)
+        N = query_cameras.shape[1]
+        photo = self._per_view(self._photo_codes('score_gradient', images, codes, self.cache.B, (1, N)), N)
         poses = query_poses(query_cameras, self.transform)
-        one = codes.shape[1] == 1 and N != 1
-        lens = self._lengths(n_context, N)
-        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
-        tm = self.transformer
-        parts = [tm.score_grad_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **lkw(a, b))
-                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
-        if not parts:
-            parts = [tm.score_grad_from_context(self.cache, poses, codes[:, :0])]      # N = 0: empty tensors of the right shapes
-        res = {k: (torch.cat([p[k] for p in parts], 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        res = self._walk(N, max_views_per_call, n_context,
+                         lambda a, b, **lkw: self.transformer.score_grad_from_context(self.cache, poses[:, a:b], photo(a, b), **lkw))
         res['poses'] = poses
         return res
 
@@ -759,21 +698,16 @@ class ViewRenderer:
         B = self.cache.B
         if cameras0 is not None:
             cameras0 = self._world_cameras('refine', cameras0)
-        codes = self._photo_codes('refine', images, codes, None if cameras0 is None else cameras0.shape[1])
+        codes = self._photo_codes('refine', images, codes, B, None if cameras0 is None else (1, cameras0.shape[1]))
         if cameras0 is None:
             cameras0 = self.localize(codes=codes, max_views_per_call=max_views_per_call, n_context=n_context)['generated_cameras']
         N = cameras0.shape[1]
+        photo = self._per_view(codes, N)
         poses = query_poses(cameras0, self.transform)
-        one = codes.shape[1] == 1 and N != 1
-        lens = self._lengths(n_context, N)
-        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
         kw = dict(steps=steps, step_xyz=step_xyz, step_rot=step_rot, return_trace=return_trace)
-        tm = self.transformer
-        parts = [tm.refine_from_context(self.cache, poses[:, a:b], codes if one else codes[:, a:b], **kw, **lkw(a, b))
-                 for a, b in plan_view_chunks(N, B, max_views_per_call)]
-        if not parts:
-            parts = [tm.refine_from_context(self.cache, poses, codes[:, :0], **kw)]
-        res = {k: (torch.cat([p[k] for p in parts], 2 if k == 'trace' else 1) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        res = self._walk(N, max_views_per_call, n_context,               # trace is [steps+1,B,N]
+                         lambda a, b, **lkw: self.transformer.refine_from_context(self.cache, poses[:, a:b], photo(a, b), **kw, **lkw),
+                         axis=dict(trace=2))
         cams = res['cameras']
         res['generated_cameras'] = geometry.from_relative_cameras(cams, self.transform) if self.transform is not None else cams
         return res
@@ -785,40 +719,20 @@ class ViewRenderer:
         ``return_tokens`` also codes int32 [B,N,t,t], pose_prediction [B,N,L,7] (the per-token poses in the context's frame) and raw
         [B,N,L,7].  N is walked in chunks of whole views (``plan_view_chunks``).  ``n_context``: as ``render``'s."""
         self._context('localize')
-        if (images is None) == (codes is None):
-            raise ValueError('localize: exactly one of images / codes expected')
-        tm, cm = self.transformer, self.codebook
-        dev = cm.device
-        B = self.cache.B
-        t = tm.config.token_image_size
-        if codes is None:
-            images = torch.as_tensor(images).to(dev)
-            if images.dim() != 5 or images.shape[0] != B:
-                raise ValueError(f'localize: images [B={B},N,H,W,3] expected, got {tuple(images.shape)}')
-            N = images.shape[1]
-            if N:
-                codes = cm.encode(_frames_for_encode(images, cm.config.image_size))[-1]
-            else:
-                codes = torch.empty((B, 0, t, t), dtype=torch.int32, device=dev)
-        else:
-            codes = torch.as_tensor(codes).to(dev)
-            if codes.dim() < 2 or codes.shape[0] != B or codes.numel() % (B * t * t) or codes.dtype.is_floating_point:
-                raise ValueError(f'localize: codes int [B={B},N,{t},{t}] expected, got {codes.dtype} {tuple(codes.shape)}')
-            N = codes.numel() // (B * t * t)
-        codes = codes.to(torch.int32).view(B, N, t, t)
+        codes = self._photo_codes('localize', images, codes, self.cache.B)
         kw = dict(return_tokens=return_tokens, **({} if self.fused_tail is None else dict(fused_tail=bool(self.fused_tail))))
-        lens = self._lengths(n_context, N)
-        lkw = lambda a, b: {} if lens is None else dict(n_context=lens[:, a:b])
-        parts = [tm.localize_from_context(self.cache, codes[:, a:b], **kw, **lkw(a, b)) for a, b in plan_view_chunks(N, B, max_views_per_call)]
-        if not parts:
-            parts = [tm.localize_from_context(self.cache, codes, **kw)]             # N = 0: empty tensors of the right shapes
-        cat = lambda ts: torch.cat(ts, 1) if len(ts) > 1 else ts[0]
-        cams = cat([p['cameras'] if return_tokens else p for p in parts])
+
+        def views(a, b, **lkw):                                          # (without return_tokens the model answers with the cameras alone)
+            out = self.transformer.localize_from_context(self.cache, codes[:, a:b], **kw, **lkw)
+            return out if return_tokens else dict(cameras=out)
+
+        out = self._walk(codes.shape[1], max_views_per_call, n_context, views)
+        cams = out['cameras']
         if self.transform is not None:                                   # evaluate_transformer.py:139-140
             cams = geometry.from_relative_cameras(cams, self.transform)
         res = dict(generated_cameras=cams)
         if return_tokens:
-            res.update(codes=codes, pose_prediction=cat([p['pose_prediction'] for p in parts]), raw=cat([p['raw'] for p in parts]))
+            res.update(codes=codes, pose_prediction=out['pose_prediction'], raw=out['raw'])
         return res
 
     def sweep(self, query_cameras, sizes=None, max_views_per_call: int = None, return_codes: bool = False):
@@ -829,13 +743,11 @@ class ViewRenderer:
         ``set_context(n_context=...)`` a size above a scene's number of valid views is that number (its padding is never read)."""
         self._context('sweep')
         B, C = self.cache.B, self.cache.C
-        query_cameras = torch.as_tensor(query_cameras, dtype=torch.float32).to(self.codebook.device)
-        if query_cameras.dim() != 3 or query_cameras.shape[0] != B or query_cameras.shape[-1] != 7:
-            raise ValueError(f'sweep: query_cameras [B={B},N,7] expected, got {tuple(query_cameras.shape)}')
+        query_cameras = self._world_cameras('sweep', query_cameras)
         N = query_cameras.shape[1]
-        sz = np.arange(C + 1) if sizes is None else np.asarray(sizes.detach().cpu().numpy() if isinstance(sizes, torch.Tensor) else sizes)
-        if sz.ndim != 1 or sz.dtype == np.bool_ or not np.issubdtype(sz.dtype, np.integer) or (sz.size and (sz.min() < 0 or sz.max() > C)):
-            raise ValueError(f'sweep: sizes, a list of integers in [0, C={C}], expected, got {sizes}')
+        sz = np.arange(C + 1) if sizes is None else _int_array('sweep: sizes', sizes)
+        if sz.size and sz.max() > C:
+            raise ValueError(f'sweep: sizes in [0, C={C}] expected, got {sizes}')
         sz = sz.astype(np.int32)
         K = sz.shape[0]
         cam, size, inverse = sweep_layout(N, K)
@@ -858,18 +770,15 @@ def evaluate_context_sizes(transformer_model, codebook_model, images, cameras):
     generated_codes [B,S,t,t], codes [B,S,t,t] — entry i being the last frame's view / pose from the first i frames as context.  All S
     frames are encoded once (as there); the S-1 context frames are prefilled once, the target camera is swept over the sizes 0 ... S-1
     and the target's code map is localized against the same sizes.  S = 1 leaves no context view: ValueError."""
-    dev = codebook_model.device
-    images = torch.as_tensor(images).to(dev)
-    cameras = torch.as_tensor(cameras, dtype=torch.float32).to(dev)
-    if images.dim() != 5 or cameras.dim() != 3 or cameras.shape[-1] != 7 or tuple(images.shape[:2]) != tuple(cameras.shape[:2]):
-        raise ValueError(f'evaluate_context_sizes: images [B,S,H,W,3] and cameras [B,S,7] expected, got {tuple(images.shape)} and '
-                         f'{tuple(cameras.shape)}')
-    B, S = images.shape[:2]
+    r = ViewRenderer(transformer_model, codebook_model)
+    images = torch.as_tensor(images).to(codebook_model.device)
+    cameras = r._world_cameras('evaluate_context_sizes', cameras, new=True)
+    B, S = cameras.shape[:2]
     if S < 2:
         raise ValueError('evaluate_context_sizes: S >= 2 expected (S - 1 context views and the target)')
     t = transformer_model.config.token_image_size
-    codes = codebook_model.encode(_frames_for_encode(images, codebook_model.config.image_size))[-1].to(torch.int32).view(B, S, t, t)
-    r = ViewRenderer(transformer_model, codebook_model).set_context(codes=codes[:, :-1], cameras=cameras[:, :-1])
+    codes = r._photo_codes('evaluate_context_sizes', images, None, B, (S,))
+    r.set_context(codes=codes[:, :-1], cameras=cameras[:, :-1])
     sizes = np.arange(S, dtype=np.int32)
     swp = r.sweep(cameras[:, -1:], sizes=sizes, return_codes=True)
     loc = r.localize(codes=codes[:, -1:].expand(B, S, t, t).contiguous(), n_context=sizes.reshape(1, S).repeat(B, 0))
@@ -878,10 +787,17 @@ def evaluate_context_sizes(transformer_model, codebook_model, images, cameras):
                 generated_codes=swp['generated_codes'][:, 0], codes=codes)
 
 
+def _with_context(transformer_model, codebook_model, images, cameras, kw, *names, **fixed):
+    """A renderer with its context set, for the one-call functions: the keywords ``codes`` and ``names`` leave ``kw`` for ``set_context``
+    (None where the caller gave none), ``fixed`` goes there as it is; what stays in ``kw`` is the method's."""
+    ctx = {k: kw.pop(k, None) for k in ('codes', *names)}
+    return ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, **ctx, **fixed)
+
+
 def render_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.render``'s
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``max_views_per_call``, ``return_codes``."""
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw)
     return r.render(query_cameras, **kw)
 
 
@@ -889,8 +805,7 @@ def sweep_views(transformer_model, codebook_model, images, cameras, query_camera
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.sweep``'s
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``n_context`` (valid context views per scene),
     ``sizes``, ``max_views_per_call``, ``return_codes``."""
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None),
-                                                                    n_context=kw.pop('n_context', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw, 'n_context')
     return r.sweep(query_cameras, **kw)
 
 
@@ -898,7 +813,7 @@ def sample_views(transformer_model, codebook_model, images, cameras, query_camer
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.sample``'s
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``n_samples``, ``temperature``, ``top_k``, ``top_p``,
     ``seed``, ``max_views_per_call``, ``return_codes``."""
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw)
     return r.sample(query_cameras, **kw)
 
 
@@ -909,9 +824,7 @@ def rollout_views(transformer_model, codebook_model, images, cameras, path_camer
     ``'e4m3'``: roll out on a growing packed context, ``set_context(pack=...)``).  The cache is allocated with room for the whole path."""
     T = int(torch.as_tensor(path_cameras).shape[1])
     C = int(torch.as_tensor(cameras).shape[1])
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None),
-                                                                    n_context=kw.pop('n_context', None), capacity=C + T,
-                                                                    pack=kw.pop('pack', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw, 'n_context', 'pack', capacity=C + T)
     return r.rollout(path_cameras, **kw)
 
 
@@ -919,7 +832,7 @@ def score_views(transformer_model, codebook_model, images, cameras, query_camera
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7], ``query_cameras`` [B,N,7] and ``photos`` uint8 [B,N,H,W,3] or
     [B,1,H,W,3] -> ``ViewRenderer.score``'s dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``photo_codes``
     (the photos' codes instead of ``photos``), ``max_views_per_call``."""
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw)
     return r.score(query_cameras, images=photos, codes=kw.pop('photo_codes', None), **kw)
 
 
@@ -928,7 +841,7 @@ def match_views(transformer_model, codebook_model, images, cameras, query_camera
     [B or 1,P,H,W,3] -> ``ViewRenderer.match``'s dict (the [B,P,M] likelihoods from M query views, best_camera, best_photo).  Keywords:
     ``codes`` (context codes instead of images; pass images=None), ``photo_codes`` (the photos' codes instead of ``photos``),
     ``max_views_per_call``, ``n_context``."""
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw)
     return r.match(query_cameras, images=photos, codes=kw.pop('photo_codes', None), **kw)
 
 
@@ -936,7 +849,7 @@ def refine_views(transformer_model, codebook_model, images, cameras, photos=None
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7], ``photos`` uint8 [B,N,H,W,3] and ``cameras0`` [B,N,7] (None:
     the localizer's estimate) -> ``ViewRenderer.refine``'s dict.  Keywords: ``codes`` (context codes instead of images; pass images=None),
     ``photo_codes`` (the photos' codes instead of ``photos``), ``steps``, ``step_xyz``, ``step_rot``, ``max_views_per_call``, ``return_trace``."""
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw)
     return r.refine(cameras0, images=photos, codes=kw.pop('photo_codes', None), **kw)
 
 
@@ -944,5 +857,5 @@ def localize_views(transformer_model, codebook_model, images, cameras, photos=No
     """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``photos`` uint8 [B,N,H,W,3] -> ``ViewRenderer.localize``'s
     dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``photo_codes`` (the photos' codes instead of
     ``photos``), ``max_views_per_call``, ``return_tokens``."""
-    r = ViewRenderer(transformer_model, codebook_model).set_context(images=images, cameras=cameras, codes=kw.pop('codes', None))
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw)
     return r.localize(images=photos, codes=kw.pop('photo_codes', None), **kw)
