@@ -535,6 +535,23 @@ int vf_sample_rows_f32(const float* logits, int64_t rows, int N, int64_t ld, flo
  * tokens as ONE fp32 chain in token order per (view, sample).  One wave per (view, sample).  NULL pointers, views < 0, L < 1, S < 1 or
  * S > 65535: VF_ERR_BAD_ARG.  views == 0 is a no-op. */
 int vf_sample_views_f32(const float* logp, int64_t views, int L, int S, float* log_likelihood, void* stream);
+/* The mean of the distribution vf_sample_rows_f32 draws from, in the codebook's latent space (csrc/mix_rows.hip): per row of fp32 logits
+ * [rows][ld >= N], with the codebook E fp32 [D][ldE >= N] in vf_codebook_gather_f32's layout (feature-major, code n is column n):
+ *   1. the kept set is vf_sample_rows_f32's: y = z / temperature, -inf has probability 0, top-k keeps ties, top-p is applied on the
+ *      top-k set and always keeps the maximum (the steps above, run by the same routine: csrc/row_filter.h);
+ *   2. p_n = e_n / sum_kept e for the kept n, e_n = e^((z_n - max z) / temperature) by vf_exp_neg; every other code has p_n = +0 exactly;
+ *   3. out[r][d] (fp32 [rows][ldo >= D]) = sum_n p_n E[d][n]: fp32 products and sums, ONE fmaf chain per element from +0 in ascending code
+ *      order (v_mfma_f32_16x16x4_f32) — a grouping that depends on N and D only, never on rows, on where the row sits or on what other
+ *      rows keep (a tile of 32 codes that none of a workgroup's 16 rows keeps is skipped: it would add exact zeros);
+ *   4. kept[r] (NULL or [rows]) and thr[r] (NULL or [rows]) have vf_sample_rows_f32's meaning and its bits;
+ *   5. a row without a finite logit gives kept 0, thr NaN and out all NaN; NaN logits are unspecified;
+ *   6. E must be finite (the caller's contract): a code that is not kept contributes an exact zero, not "nothing".
+ * With top_k = 1 and a unique maximum out is vf_codebook_gather_f32 of the arg-max, bit for bit.  Footprint: reads columns 0..N-1 of each
+ * row of the logits and of each of E's D rows; writes rows x D elements of out and rows of kept / thr.  No atomics, no workspace.
+ * NULL logits / E / out, rows < 0, N < 1, ld < N, ldE < N, D < 1, ldo < D, temperature <= 0 or not finite, top_p <= 0 or NaN, top_k < 0:
+ * VF_ERR_BAD_ARG; N > 1024, D % 32 != 0 or D > 256: VF_ERR_UNSUPPORTED; both before any launch.  rows == 0 is a no-op. */
+int vf_mix_rows_f32(const float* logits, int64_t rows, int N, int64_t ld, float temperature, int top_k, float top_p, const float* E, int D,
+                    int64_t ldE, float* out, int64_t ldo, int32_t* kept, float* thr, void* stream);
 /* host-side CRC-32C (Castagnoli) of a HOST buffer, for the TFRecord / TensorBundle files of the reference's datasets and
  * Keras checkpoints (viewformer_amd/codes_dataset.py, checkpoint.py); crc = 0 starts a new checksum */
 uint32_t vf_crc32c(const void* data, size_t n, uint32_t crc);

@@ -138,6 +138,7 @@ EXPORTS = {
     'vf_match_views_f32': (c_int, [P, c_int64, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, P, P, P]),
     'vf_sample_rows_f32': (c_int, [P, c_int64, c_int, c_int64, c_float, c_int, c_float, ctypes.c_uint32, P, c_int, P, P, P, P, P]),
     'vf_sample_views_f32': (c_int, [P, c_int64, c_int, c_int, P, P]),
+    'vf_mix_rows_f32': (c_int, [P, c_int64, c_int, c_int64, c_float, c_int, c_float, P, c_int, c_int64, P, c_int64, P, P, P]),
     'vf_argmax_rows_f32': (c_int, [P, c_int64, c_int, c_int, P, P]),
     'vf_postprocess_u8': (c_int, [P, P, c_int64, P]),
     'vf_resize_u8': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),

@@ -11,16 +11,8 @@
 //   5. idx = arg-max over the kept n of y_n + g_n, lowest index on equal keys (Gumbel-max: an exact draw from the soft-max of the kept set)
 //   6. logp = y_idx - (max y + log sum_kept e_n)
 //
-// One wave per row.  N <= 1024: the row is read ONCE into registers (16 values per lane, lane-strided, coalesced; slots beyond N hold
-// -inf, which nothing keeps) together with d_n = (z_n - max z) / T and e_n = e^d_n (exp_neg: lmhead_score.hip's, moved to vf_common.h), both
-// computed once per row.  N > 1024: every pass re-reads the row (from cache) and recomputes d and e.  Everything after the read is
-// wave-local: no LDS, no atomics.
-//
-// Thresholds are found on the ORDER-PRESERVING INTEGER IMAGE of the fp32 logits (sign bit flipped for positives, all bits for negatives:
-// unsigned order = float order; dividing by T > 0 keeps the order, so the search runs on z and never sees a rounding): 32 steps from the
-// top bit down, each step one masked count (top-k; ballots) or one masked mass (top-p; per-lane partial sums in slot order, then
-// vf_wave_sum's butterfly).  Floating-point addition is monotone in each summand, so the mass in this FIXED order is monotone in the
-// threshold and the search finds the largest threshold whose mass reaches the target — a value of the row.
+// One wave per row.  The kept set — the read, d and e once per row, the bitwise threshold searches on the order-preserving integer image of
+// the logits — is row_filter.h's vf_row_filter, shared with mix_rows.hip; the draws below walk the same registers with its VF_ROW_FOR.
 //
 // The key of the arg-max is d_n + g_n, not y_n + g_n: the same arg-max in exact arithmetic (a shift by max y), without |max y| in the
 // rounding of the sum; logp = d_idx - log(sum_kept e) likewise.  -log u is formed as -log1p(-(1 - u)): 1 - u is exact in fp32 and the
@@ -29,19 +21,12 @@
 // A row's outputs depend on its logits, the parameters, seed and row_id only: not on rows, on where the row sits, on ld, on S (sample s of
 // any launch is sample s) or on the optional outputs requested.
 #include "vf_common.h"
+#include "row_filter.h"
 #include "../../include/vf_hip.h"
 
 namespace {
 
 constexpr uint32_t SITE_SAMPLE = 0x5A0000u;
-constexpr uint32_t IMG_NEG_INF = 0x007FFFFFu;             // image of -inf: below every finite value's
-
-// unsigned image of a float with the floats' order (no NaN; -0 is canonicalised to +0 by the caller)
-__device__ __forceinline__ uint32_t img_of(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float img_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
 // g = -log(-log u), u = ((w >> 9) + 0.5) 2^-23 in (0, 1): 1 - u is exact, -log u = -log1p(-(1 - u))
 __device__ __forceinline__ float gumbel_of(uint32_t w) {
@@ -49,32 +34,6 @@ __device__ __forceinline__ float gumbel_of(uint32_t w) {
     const float a = __fsub_rn(1.0f, u);
     return -logf(-log1pf(-a));
 }
-
-// Visits every element of the wave's row with (c, k, d, e) = (column, image of z, (z - max z) / T, e^d) in scope; all 64 lanes stay
-// active (ballots and shuffles inside BODY are whole-wave).  REG: the 16 register slots; otherwise a pass over memory.
-#define VF_ROW_FOR(...)                                                                                                       \
-    if constexpr (REG) {                                                                                                        \
-        _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                                                        \
-            const int c = lane + 64 * j;                                                                                        \
-            const uint32_t k = kimg[j];                                                                                         \
-            const float d = dd[j], e = ee[j];                                                                                   \
-            (void)c; (void)k; (void)d; (void)e;                                                                                 \
-            __VA_ARGS__                                                                                                         \
-        }                                                                                                                       \
-    } else {                                                                                                                    \
-        for (int c0 = 0; c0 < n; c0 += 64) {                                                                                    \
-            const int c = c0 + lane;                                                                                            \
-            const float zc = c < n ? __fadd_rn(xr[c], 0.0f) : -INFINITY;                                                        \
-            const uint32_t k = img_of(zc);                                                                                      \
-            const float d = __fdiv_rn(__fsub_rn(zc, zmax), T);                                                                  \
-            const float e = k > IMG_NEG_INF ? exp_neg_clamped(d) : 0.0f;                                                        \
-            (void)k; (void)d; (void)e;                                                                                          \
-            __VA_ARGS__                                                                                                         \
-        }                                                                                                                       \
-    }
-
-// e^d for d <= 0; arguments whose result is below the normal range anyway never reach exp_neg (d log2(e) would overflow for huge |d|)
-__device__ __forceinline__ float exp_neg_clamped(float d) { return d >= -88.0f ? vf_exp_neg(d) : 0.0f; }
 
 template <bool REG>
 __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ x, long long rows, int n, long long ld, float T, int top_k,
@@ -87,23 +46,12 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
     const float* xr = x + (size_t)row * ld;
     const uint64_t rid = row_id ? (uint64_t)row_id[row] : (uint64_t)row;
 
-    // ---- the read (REG: the only one) and the row's maximum
+    // ---- the kept set: its threshold's image t and its mass (row_filter.h)
     uint32_t kimg[16];
     float dd[16], ee[16];
-    float zmax = -INFINITY;
-    if constexpr (REG) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int c = lane + 64 * j;
-            dd[j] = c < n ? __fadd_rn(xr[c], 0.0f) : -INFINITY;              // -0 -> +0: one image per value
-            zmax = fmaxf(zmax, dd[j]);
-        }
-    } else {
-        for (int c = lane; c < n; c += 64) zmax = fmaxf(zmax, xr[c]);
-        zmax = __fadd_rn(zmax, 0.0f);
-    }
-    zmax = vf_wave_max(zmax);
-    if (zmax == -INFINITY) {                                                // no finite logit: no distribution (uniform over the wave)
+    float zmax, mass;
+    uint32_t t;
+    if (!vf_row_filter<REG>(xr, n, lane, T, top_k, top_p, kimg, dd, ee, zmax, t, mass)) {      // no finite logit: no distribution
         for (int s = lane; s < S; s += 64) {
             idx_out[(size_t)row * S + s] = -1;
             if (logp_out) logp_out[(size_t)row * S + s] = __builtin_nanf("");
@@ -114,67 +62,13 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
         }
         return;
     }
-    if constexpr (REG) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float zc = dd[j];
-            kimg[j] = img_of(zc);
-            dd[j] = __fdiv_rn(__fsub_rn(zc, zmax), T);
-            ee[j] = kimg[j] > IMG_NEG_INF ? exp_neg_clamped(dd[j]) : 0.0f;
-        }
-    }
-    const uint32_t kmax = img_of(zmax);
-
-    // ---- top-k: the image of the k-th largest value, or of the smallest finite one where top-k does not apply
-    int nfinite = 0;
-    uint32_t kmin = 0xFFFFFFFFu;
-    VF_ROW_FOR(nfinite += __popcll(__ballot(k > IMG_NEG_INF)); kmin = k > IMG_NEG_INF && k < kmin ? k : kmin;)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t ok = (uint32_t)__shfl_xor((int)kmin, o, 64);
-        kmin = ok < kmin ? ok : kmin;
-    }
-    uint32_t t = kmin;
-    if (top_k > 0 && top_k < nfinite) {
-        t = 0;
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t cand = t | (1u << bit);
-            int cnt = 0;
-            VF_ROW_FOR(cnt += __popcll(__ballot(k >= cand));)
-            t = cnt >= top_k ? cand : t;
-        }
-    }
-
-    // ---- top-p: the largest threshold whose mass reaches top_p x the mass top-k left
-    float mass;
-    {
-        float part = 0.f;
-        VF_ROW_FOR(part = __fadd_rn(part, k >= t ? e : 0.0f);)
-        mass = vf_wave_sum(part);
-    }
-    if (top_p < 1.0f) {
-        const float target = __fmul_rn(top_p, mass);
-        const uint32_t tk = t;
-        uint32_t tp = 0;
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t cand = tp | (1u << bit);
-            float part = 0.f;
-            VF_ROW_FOR(part = __fadd_rn(part, (k >= cand && k >= tk) ? e : 0.0f);)
-            tp = vf_wave_sum(part) >= target ? cand : tp;
-        }
-        tp = tp > kmax ? kmax : tp;                                          // the maximum is always kept
-        t = tp > tk ? tp : tk;
-        float part = 0.f;
-        VF_ROW_FOR(part = __fadd_rn(part, k >= t ? e : 0.0f);)
-        mass = vf_wave_sum(part);
-    }
     const float lsum = logf(mass);                                           // mass >= 1: the maximum's e is exactly 1
     if (kept_out || thr_out) {
         int cnt = 0;
         VF_ROW_FOR(cnt += __popcll(__ballot(k >= t));)
         if (lane == 0) {
             if (kept_out) kept_out[row] = cnt;
-            if (thr_out) thr_out[row] = __fdiv_rn(img_inv(t), T);
+            if (thr_out) thr_out[row] = __fdiv_rn(vf_img_inv(t), T);
         }
     }
 

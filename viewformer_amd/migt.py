@@ -784,6 +784,44 @@ class MIGT:
             res['logits'] = lg.view(B, N, *tshape, nE)
         return res
 
+    def expect_from_context(self, cache, query_cameras, embedding, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, n_context=None):
+        """The EXPECTED view per query camera, in the codebook's latent space: ``query_cameras`` fp32 [B,N,7] in the context's (relative,
+        normalised) frame and ``embedding`` fp32 [D, n_embeddings] on the device (``VQGAN.codebook_embedding()``) -> dict of
+            latents  fp32  [B,N,t,t,D]  sum over the kept codes of p_n embedding[:, n] per token
+            kept     int32 [B,N,t,t]    the size of the set each token's mean runs over
+        A MASK view's tokens are independent given the context, so the mean of the distribution ``sample_from_context`` draws from (same
+        ``temperature``, ``top_k``, ``top_p``) is known per token in closed form.  The launches are
+        ``generate_from_context(codes_only=False)``'s — same pose embedding, ``_query_rows`` and ``_lm`` — followed by one row kernel
+        (ops.mix_rows).  ``top_k = 1`` gives the embedding of ``generate_from_context``'s codes, bit for bit, on every token with a unique
+        maximum.  There is no fallback: a shape the kernel does not take is refused.
+        ``n_context``: how many leading context views each query sees (``_context_lengths``; None: all C, the launches without the
+        keyword); consecutive views share an attention group, which costs what its longest member costs."""
+        if isinstance(top_k, bool) or int(top_k) != top_k:
+            raise ValueError(f'expect_from_context: an integer top_k expected, got {top_k}')
+        self._sampler_args('expect_from_context', 1, temperature, top_k, top_p)
+        nE = self.config.n_embeddings
+        if (not torch.is_tensor(embedding) or embedding.dim() != 2 or embedding.dtype != torch.float32 or embedding.shape[1] != nE
+                or not embedding.is_contiguous()):
+            raise ValueError(f'expect_from_context: embedding fp32 [D, n_embeddings={nE}] (contiguous) expected, got '
+                             f'{tuple(embedding.shape) if torch.is_tensor(embedding) else type(embedding).__name__}')
+        own = self.device
+        if own is not None and (embedding.device.type != own.type or (own.index is not None and embedding.device.index != own.index)):
+            raise ValueError(f"expect_from_context: the embedding lives on {embedding.device}, the model on {self.device}")
+        D = embedding.shape[0]
+        if not ops.mix_rows_supported(D, nE):
+            raise ValueError(f'expect_from_context: no mix kernel for D = {D}, n_embeddings = {nE} (D % 32 == 0, D <= 256, n_embeddings <= 1024)')
+        query_cameras, _, N, L, ctx = self._context_args('expect_from_context', cache, query_cameras, n_context=n_context)
+        dev, B, tshape = self.device, cache.B, cache.tshape
+        M = B * N * L
+        if N == 0:
+            return dict(latents=torch.empty((B, 0, *tshape, D), dtype=torch.float32, device=dev),
+                        kept=torch.empty((B, 0, *tshape), dtype=torch.int32, device=dev))
+        hf = self._query_rows(cache, *self._mask_rows(query_cameras, L), N, ctx)
+        lg = torch.empty((M, nE), dtype=torch.float32, device=dev)
+        self._lm(hf, M, lg)                                                  # migt.py:417
+        st = ops.mix_rows(lg, M, nE, embedding, D, temperature=temperature, top_k=top_k, top_p=top_p, want=('out', 'kept'))
+        return dict(latents=st['out'].view(B, N, *tshape, D), kept=st['kept'].view(B, N, *tshape))
+
     def localize_from_context(self, cache, codes, return_tokens: bool = False, fused_tail: bool = True, n_context=None):
         """Localize N photos per scene against a prefilled context: ``codes`` int [B,N,t,t] (the photos' code maps) -> cameras fp32
         [B,N,7] in the context's (relative, normalised) frame; with ``return_tokens`` a dict(cameras, pose_prediction [B,N,L,7],

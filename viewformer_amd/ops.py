@@ -1008,6 +1008,40 @@ def sample_views(logp, views, L, n_samples):
     return ll
 
 
+MIX_OUTPUTS = ('out', 'kept', 'thr')
+MIX_ROWS_PER_GROUP = 16          # rows that share one workgroup's codebook tiles (csrc/mix_rows.hip); no result depends on it
+
+
+def mix_rows_supported(D, N):
+    """the shapes vf_mix_rows_f32 takes: the row in registers and D in whole pairs of 16-feature MFMA tiles"""
+    return 1 <= int(N) <= 1024 and 1 <= int(D) <= 256 and int(D) % 32 == 0
+
+
+def mix_rows(logits, rows, N, E, D, temperature=1.0, top_k=0, top_p=1.0, ld=None, ldE=None, want=('out',)):
+    """The mean of the distribution ``sample_rows`` draws from, in the codebook's latent space (vf_mix_rows_f32; include/vf_hip.h has the
+    definitions): fp32 logits [rows][ld >= N] and the codebook ``E`` fp32 [D][ldE >= N] (``codebook_gather``'s layout) -> a dict of the
+    outputs named in ``want`` (MIX_OUTPUTS): out fp32 [rows, D] = sum over the kept codes of p_n E[:, n], kept int32 [rows] and thr fp32
+    [rows] (``sample_rows``' bits).  ``top_k = 1`` is ``codebook_gather`` of the arg-max."""
+    want = tuple(want)
+    if not want or any(w not in MIX_OUTPUTS for w in want):
+        raise ValueError(f'want: a non-empty subset of {MIX_OUTPUTS} expected, got {want}')
+    _f32(logits, 'logits')
+    _f32(E, 'E')
+    ldv, ldEv = N if ld is None else int(ld), N if ldE is None else int(ldE)
+    if rows < 0 or N < 1 or ldv < N or not logits.is_contiguous() or logits.numel() < (rows - 1) * ldv + N * (rows > 0):
+        raise ValueError(f'logits: {rows} contiguous rows of {N} with ld {ldv} expected, got {tuple(logits.shape)}')
+    if D < 1 or ldEv < N or not E.is_contiguous() or E.numel() < (D - 1) * ldEv + N:
+        raise ValueError(f'E: {D} contiguous rows of {N} with ldE {ldEv} expected, got {tuple(E.shape)}')
+    dev = logits.device
+    shapes = dict(out=((rows, D), torch.float32), kept=((rows,), torch.int32), thr=((rows,), torch.float32))
+    out = {w: torch.empty(shapes[w][0], dtype=shapes[w][1], device=dev) for w in MIX_OUTPUTS if w == 'out' or w in want}
+    if rows == 0:                                                    # (an empty batch owns no memory: its pointers are null)
+        return {w: out[w] for w in want}
+    check(_lib.load().vf_mix_rows_f32(_p(logits), rows, N, ldv, float(temperature), int(top_k), float(top_p), _p(E), D, ldEv,
+                                      _p(out['out']), D, _p(out.get('kept')), _p(out.get('thr')), _stream()), 'vf_mix_rows_f32')
+    return {w: out[w] for w in want}
+
+
 def postprocess_u8(x):
     x = _f32(x).contiguous()
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)

@@ -13,6 +13,7 @@ and values are computed once (``MIGT.prefill_context``) and each query is a sing
     est = r.localize(images=photos_u8)                       # est['generated_cameras'] fp32 [B,N,7], the caller's world frame
     fit = r.score(candidate_cameras, images=photo_u8)        # fit['log_likelihood'] fp32 [B,N]: how well the photo fits each camera
     alt = r.sample(query_cameras, n_samples=8, top_p=0.9)    # alt['generated_images'] uint8 [B,N,8,H,W,3]: draws, with their log-likelihood
+    avg = r.render_mean(query_cameras, top_p=0.9)            # avg['generated_images'] uint8 [B,N,H,W,3]: the mean of those draws' latents, decoded once
     r.append(images=new_frames_u8, cameras=new_cams)         # new photographs: the context grows by K views, no earlier view is run again
     fly = r.rollout(path_cameras)                            # fly['generated_images'] uint8 [B,T,H,W,3]: frame t sees the photos AND frames 0..t-1
 
@@ -465,14 +466,16 @@ class ViewRenderer:
                        logits=out['logits'].view(*lead, t, t, out['logits'].shape[-1]))
         return res
 
-    def _decode(self, flat, keep_decoded: bool = False):
-        """code maps int [n,t,t] -> (images uint8 [n,H,W,3], the decoder's fp32 output [n,H,W,3] or None), decoded in chunks of
-        MAX_SCENES_PER_CALL maps as the evaluators do"""
+    def _decode(self, flat, keep_decoded: bool = False, latents: bool = False):
+        """code maps int [n,t,t] — or, with ``latents``, latent maps fp32 [n,t,t,D] — -> (images uint8 [n,H,W,3], the decoder's fp32
+        output [n,H,W,3] or None), decoded in chunks of MAX_SCENES_PER_CALL maps as the evaluators do (``codebook.decode_code``; latents:
+        ``codebook.decode``, which takes them in the model's ``data_format``)"""
         cm = self.codebook
         dev = cm.device
         decs, imgs = [], []
         for a in range(0, flat.shape[0], MAX_SCENES_PER_CALL):
-            dec = cm.decode_code(flat[a:a + MAX_SCENES_PER_CALL])
+            part = flat[a:a + MAX_SCENES_PER_CALL]
+            dec = cm.decode(part.permute(0, 3, 1, 2) if cm.data_format == 'NCHW' else part) if latents else cm.decode_code(part)
             if cm.data_format == 'NCHW':
                 dec = dec.permute(0, 2, 3, 1)
             dec = dec.contiguous()
@@ -557,6 +560,40 @@ class ViewRenderer:
         res = dict(generated_images=img.view(B, N, S, *img.shape[1:]), log_likelihood=out['log_likelihood'])
         if return_codes:
             res.update(generated_codes=out['codes'], token_log_prob=out['token_log_prob'], kept=out['kept'])
+        return res
+
+    def render_mean(self, query_cameras, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, max_views_per_call: int = None,
+                    return_latents: bool = False, n_context=None):
+        """The EXPECTED view per camera: ``query_cameras`` [B,N,7] in the caller's world frame (the context's) -> dict(generated_images
+        uint8 [B,N,H,W,3], kept int32 [B,N,t,t]: the size of the set each token's mean runs over); with ``return_latents`` also latents
+        fp32 [B,N,t,t,D] and decoded (the decoder's fp32 output [B,N,H,W,3]).  A MASK view's tokens are independent given the context,
+        so the mean of the distribution ``sample`` draws from (same ``temperature``, ``top_k``, ``top_p``) is known per token in the
+        codebook's latent space, q = sum over the kept codes of p_n E[:, n] (``MIGT.expect_from_context``), and costs ONE decode
+        (``codebook.decode``, in chunks of MAX_SCENES_PER_CALL views) where averaging S samples costs S.  Where the model is guessing
+        the arg-max view commits to one code and the mean view shows the blur; along a camera path it is a continuous function of the
+        logits.  ``top_k = 1`` is ``render``, bit for bit, on tokens with a unique maximum.  The codebook must expose
+        ``codebook_embedding()``.  N is walked in chunks of whole views (``plan_view_chunks``); a view's result does not depend on the
+        chunking.  ``n_context``: as ``render``'s."""
+        self._context('render_mean')
+        query_cameras = self._world_cameras('render_mean', query_cameras)
+        if (not (0 < float(temperature) < float('inf')) or not float(top_p) > 0 or isinstance(top_k, bool) or int(top_k) != top_k
+                or int(top_k) < 0):
+            raise ValueError(f'render_mean: temperature > 0 (finite), top_p > 0 and an integer top_k >= 0 expected, got {temperature}, '
+                             f'{top_p}, {top_k}')
+        temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+        cm, tm = self.codebook, self.transformer
+        if not callable(getattr(cm, 'codebook_embedding', None)):
+            raise TypeError('render_mean: the codebook model must expose codebook_embedding() (the fp32 [embed_dim, n_embed] device tensor)')
+        B, N = self.cache.B, query_cameras.shape[1]
+        t = tm.config.token_image_size
+        poses = query_poses(query_cameras, self.transform)
+        E = cm.codebook_embedding()
+        kw = dict(temperature=temperature, top_k=top_k, top_p=top_p)
+        out = self._walk(N, max_views_per_call, n_context, lambda a, b, **lkw: tm.expect_from_context(self.cache, poses[:, a:b], E, **kw, **lkw))
+        img, dec = self._decode(out['latents'].reshape(B * N, t, t, out['latents'].shape[-1]), keep_decoded=return_latents, latents=True)
+        res = dict(generated_images=img.view(B, N, *img.shape[1:]), kept=out['kept'])
+        if return_latents:
+            res.update(latents=out['latents'], decoded=dec.view(B, N, *dec.shape[1:]))
         return res
 
     def score(self, query_cameras, images=None, codes=None, max_views_per_call: int = None, n_context=None):
@@ -815,6 +852,14 @@ def sample_views(transformer_model, codebook_model, images, cameras, query_camer
     ``seed``, ``max_views_per_call``, ``return_codes``."""
     r = _with_context(transformer_model, codebook_model, images, cameras, kw)
     return r.sample(query_cameras, **kw)
+
+
+def mean_views(transformer_model, codebook_model, images, cameras, query_cameras, **kw):
+    """One call: context ``images`` uint8 [B,C,H,W,3] + ``cameras`` [B,C,7] and ``query_cameras`` [B,N,7] -> ``ViewRenderer.render_mean``'s
+    dict.  Keywords: ``codes`` (context codes instead of images; pass images=None), ``temperature``, ``top_k``, ``top_p``,
+    ``max_views_per_call``, ``return_latents``."""
+    r = _with_context(transformer_model, codebook_model, images, cameras, kw)
+    return r.render_mean(query_cameras, **kw)
 
 
 def rollout_views(transformer_model, codebook_model, images, cameras, path_cameras, **kw):

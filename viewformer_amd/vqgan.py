@@ -465,6 +465,12 @@ class VQGAN:
         out = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
         return out.permute(0, 3, 1, 2) if self.data_format == 'NCHW' else out
 
+    def codebook_embedding(self):
+        """the codebook ``decode_code`` gathers from: the fp32 device tensor [embed_dim, n_embed] itself (feature-major, code n is column
+        n: ``ops.codebook_gather``'s and ``ops.mix_rows``' layout), not a copy — read it, do not write it"""
+        self._require_ready()
+        return self._E
+
     def decode(self, quant):
         """VQGAN.decode (vqgan_th.py:385-388); quant in the model's data_format."""
         self._require_ready()
